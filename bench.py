@@ -6,6 +6,11 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --config 4|5          # BASELINE configs 4 / 5 (InstructBLIP-Vicuna-7B, LLaVA-NeXT-Mistral-7B fp8) at engine level
+    python bench.py ... --full            # + determinism check, one-image-at-a-time legs, isolated-kernel roofline leg, CPU baseline
+    python bench.py ... --dump-outputs D  # + D/token_ids.npy: the ids the last timed step's images got back (float64, one row per image)
+
+A plain run sets up, warms up, times the --steps steps and prints the line; its `single_stream*`, `roofline`, `determinism_check` and
+`cpu_baseline` entries are null.  --full adds those legs after the timed steps (the determinism check inside the warm-up).
 
 One "step" = one batch of images (default 64 per GPU, lanes over one set of weights) through the drop-in class's `generate()` path: vision
 front-end (CLIP-L/14-336; config 4: EVA ViT-g + Q-Former; config 5: CLIP over 5 anyres tiles) + LM prefill (576 visual + 32 prompt
@@ -455,7 +460,15 @@ def main() -> int:
     ap.add_argument("--no-roofline", action="store_true", help="skip the isolated-kernel leg (libdropdec_tools.so)")
     ap.add_argument("--no-determinism-check", action="store_true", help="skip the warm-up's repeat of batch 0 from the same seeds")
     ap.add_argument("--no-build", action="store_true", help="never compile: raise when libdropdec.so is stale (for runs under a profiler)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the warm-up's determinism check, the one-image-at-a-time legs, "
+                         "the isolated-kernel roofline leg and the CPU baseline (each still switched off by its own --no-* / --single-images 0)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the generated token ids of its images, as float64) "
+                         "to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.config == 1:
         args.original = True
     if args.config == 2:
@@ -522,6 +535,9 @@ def main() -> int:
     # ------------------------------------------------------------------------------------------------------------------
     kshard = None
     from dropoutdecoding_amd.vlm import GroupPipeline
+    # from_synthetic draws the vision tower's and the projector's random-init weights from torch's global generators: seed them, so that
+    # the same arguments give the same weights (and outputs, --dump-outputs) from run to run
+    torch.manual_seed(0)
     wname, weight_bytes = "bf16", 2.0
     if args.config == 4:
         from dropoutdecoding_amd.instructblip import CustomInstructBlipForConditionalGeneration
@@ -577,17 +593,21 @@ def main() -> int:
         kw = batch_inputs(i, 1)[0]
         o = model.generate(**kw, max_new_tokens=args.n_new, eos_token_id=[])
         assert o.shape[1] == (1 if args.config == 4 else kw["input_ids"].shape[1]) + args.n_new      # InstructBLIP returns BOS + new ids
+        return o
 
     def run_steps(first, n):
+        """n steps from batch `first` on; returns what the last step's generate() calls returned (one id tensor per image)."""
         if pipe is None:
+            outs = None
             for i in range(n):
-                one_stream(first + i)
-            return
-        done = 0
+                outs = [one_stream(first + i)]
+            return outs
+        done, outs = 0, None
         for outs in pipe.run((batch_inputs(first + i) for i in range(n)), max_new_tokens=args.n_new, eos_token_id=[]):
             assert len(outs) == B and all(o.shape[1] == (1 if args.config == 4 else prompt_len) + args.n_new for o in outs)
             done += 1
         assert done == n
+        return outs
 
     img0 = rank * 10_000 if args.mode == "replicas" else 0
 
@@ -609,17 +629,23 @@ def main() -> int:
                 "same_tokens": not differing, "first_differing_images": differing[:8]}
 
     det = None
-    if pipe is not None and rank == 0 and args.warmup > 0 and not args.no_determinism_check:
+    if args.full and pipe is not None and rank == 0 and args.warmup > 0 and not args.no_determinism_check:
         det = determinism_check()
     run_steps(img0, args.warmup)
     if kshard is not None:
         kshard.exchange_ms(reset=True)
     barrier()
     t0 = time.perf_counter()
-    run_steps(img0 + args.warmup, args.steps)
+    last_outs = run_steps(img0 + args.warmup, args.steps)
     barrier()
     dt = time.perf_counter() - t0
     exchange = kshard.exchange_ms(reset=True) if kshard is not None else None
+    if args.dump_outputs and rank == 0:
+        # the ids every image of the last timed step got back from generate() (prompt + new ids; InstructBLIP: BOS + new ids), one row per
+        # image in batch order; float64 holds every id exactly
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        ids = torch.cat([o.reshape(1, -1).cpu() for o in last_outs]).numpy().astype(np.float64)
+        np.save(os.path.join(args.dump_outputs, "token_ids.npy"), ids)
 
     # ---- one image at a time (the reference's own loop: chair_test.py:274-346): adaptive speculation, always, never -------------
     def single_leg(mode, first, images):
@@ -640,7 +666,7 @@ def main() -> int:
                 "sweeps_per_step": None if st["sweeps_per_step"] is None else round(st["sweeps_per_step"], 3)}
 
     single = single_two = single_keep = None
-    if B > 1 and rank == 0 and args.single_images > 0 and args.mode == "replicas":
+    if args.full and B > 1 and rank == 0 and args.single_images > 0 and args.mode == "replicas":
         single = single_leg("adaptive", img0 + 900, args.single_images)
         single["note"] = ("one image at a time: " + front + "prefill + scorer + ensemble steps; a step is ONE sweep over the weights when the masks "
                           "sampled for an empty keep set stand (speculative step, exact), two otherwise; the library's adaptive policy stops speculating "
@@ -673,7 +699,7 @@ def main() -> int:
     if rider or rider_hp:
         dom_rows = 72
     roof = None
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         try:
             roof = roofline_leg(lm_cfg, family, wname, "fp16", T0, L, dom_rows, rows8, wide, "c5_" if args.config == 5 else "")
         except Exception as e:                                         # the throughput number must still be reported
@@ -770,7 +796,7 @@ def main() -> int:
                                               else "one rank per GPU; backend nccl = RCCL over xGMI")}
         if exchange is not None:
             line["kshard_exchange"] = exchange
-        if world == 1 and not args.no_cpu_baseline and args.config in (1, 2, 3):   # the CPU leg restates config 3's shapes
+        if args.full and world == 1 and not args.no_cpu_baseline and args.config in (1, 2, 3):   # the CPU leg restates config 3's shapes
             try:
                 line["cpu_baseline"] = cpu_baseline(max(K_eff, 1) if not args.original else 0)
             except Exception as e:                                     # the GPU number must still be reported

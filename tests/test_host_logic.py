@@ -169,6 +169,17 @@ def test_bench_gpus_n_starts_its_own_ranks_before_any_gpu_call(monkeypatch):
     assert env["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_options_full_and_dump_outputs():
+    """The plain run's switches: --full and --dump-outputs exist, and a run without a timed step is refused before anything starts."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    h = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert h.returncode == 0 and "--full" in h.stdout and "--dump-outputs" in h.stdout
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
 def test_bench_takes_its_committed_profile_from_the_rounds_own_files(tmp_path, monkeypatch):
     """`roofline.traffic` / `kernel_stats_avg_us` come from profiles/rNN_pmc_summary.json and rNN_kernel_stats.csv of the newest round (config 5:
     rNN_c5_*) — not from any other file that merely ends in the same words (round 4: a tool's r04_prefill_ab_*_kernel_stats.csv sorted last and

@@ -20,7 +20,7 @@ import bench
 json.dump({'decode_sources_sha256': bench.decode_sources_hash(), 'files': bench.DECODE_SOURCES}, open('$OUT/${R}_sources.json', 'w'), indent=1)"
 if [ "$WHAT" = stats ]; then
   rm -rf /tmp/${R}_stats
-  timeout 1000 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/${R}_stats -- python3 bench.py --steps 1 --warmup 0 --n-new 32 --no-cpu-baseline --no-roofline --single-images 1 > $OUT/${R}_bench_under_rocprof.log 2>&1
+  timeout 1000 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/${R}_stats -- python3 bench.py --full --steps 1 --warmup 0 --n-new 32 --no-cpu-baseline --no-roofline --single-images 1 > $OUT/${R}_bench_under_rocprof.log 2>&1
   echo "rocprof rc=$?"
   f=$(find /tmp/${R}_stats -name "*kernel_stats.csv" | head -1)
   head -70 "$f" > $OUT/${R}_kernel_stats.csv
