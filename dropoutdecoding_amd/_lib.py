@@ -17,6 +17,7 @@ SYMBOLS = [
     "dd_lm_prefill", "dd_lm_prefill_group", "dd_lm_decode_step_sync", "dd_lm_set_speculation", "dd_lm_spec_stats", "dd_lm_prefill_ensemble", "dd_lm_truncate", "dd_lm_prefill_extend", "dd_lm_decode_step", "dd_lm_step_base", "dd_lm_step_members", "dd_lm_step_commit",
     "dd_lm_xchg_stride", "dd_lm_xchg_export_ids", "dd_lm_xchg_import_ids",
     "dd_lm_xchg_export_winner", "dd_lm_xchg_import_winner", "dd_lm_get", "dd_lm_peek_tokens", "dd_lm_set_next_token", "dd_lm_set_eos", "dd_lm_step_algorithmic_bytes",
+    "dd_lm_set_record", "dd_record_bytes", "dd_record_field",
     "dd_set_tuning",
     "dd_lm_tp_link", "dd_lm_tp_set_exchange", "dd_lm_tp_prefill", "dd_lm_tp_decode_step",
     "dd_vit_create", "dd_vit_destroy", "dd_vit_load_tensor", "dd_vit_forward",
@@ -189,6 +190,10 @@ def _open(path: str) -> C.CDLL:
     lib.dd_lm_peek_tokens.restype = C.c_int
     lib.dd_lm_step_algorithmic_bytes.argtypes = [vp, C.c_int]
     lib.dd_lm_step_algorithmic_bytes.restype = C.c_double
+    lib.dd_lm_set_record.argtypes = [vp, vp, C.c_int, vp, C.c_size_t, vp]
+    lib.dd_record_bytes.argtypes = []
+    lib.dd_record_bytes.restype = C.c_size_t
+    lib.dd_record_field.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.dd_set_tuning.argtypes = [C.c_int, C.c_int]
     lib.dd_lm_tp_link.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
     lib.dd_lm_tp_set_exchange.argtypes = [vp, vp, C.c_size_t, TP_EXCHANGE_FN, vp]
@@ -205,6 +210,33 @@ def _open(path: str) -> C.CDLL:
     if os.environ.get("DD_NO_GRAPH", "0") not in ("", "0"):
         lib.dd_set_tuning(8, 0)          # launch every decode step kernel by kernel instead of replaying hipGraphs
     return lib
+
+
+_record_dtype = None
+
+
+def record_dtype():
+    """numpy structured dtype of one generation record, built from the library's own description of the layout
+    (dd_record_field / dd_record_bytes, include/dropdec.h "Generation record"); host only, no GPU involved."""
+    global _record_dtype
+    if _record_dtype is None:
+        import numpy as np
+        lib = load()
+        names, formats, offsets = [], [], []
+        i = 0
+        while True:
+            name, off, cnt, fl = C.c_char_p(), C.c_int(), C.c_int(), C.c_int()
+            if lib.dd_record_field(i, C.byref(name), C.byref(off), C.byref(cnt), C.byref(fl)) != 0:
+                break
+            base = "<f4" if fl.value else "<i4"
+            names.append(name.value.decode())
+            formats.append(base if cnt.value == 1 else (base, (cnt.value,)))
+            offsets.append(off.value)
+            i += 1
+        if not names:
+            raise DDError("dd_record_field describes no field")
+        _record_dtype = np.dtype({"names": names, "formats": formats, "offsets": offsets, "itemsize": int(lib.dd_record_bytes())})
+    return _record_dtype
 
 
 def check(rc: int, what: str = "", lib=None) -> None:

@@ -25,7 +25,7 @@ ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libdropdec.so")
 TOOLS_LIB = os.path.join(HERE, "libdropdec_tools.so")
 TOOLS_SOURCES = ["dd_tools.hip"]      # only in libdropdec_tools.so
-SOURCES = ["dd_dropout.hip", "dd_lm_kernels.hip", "dd_gemv.hip", "dd_attn_decode.hip", "dd_prefill.hip", "dd_engine.hip", "dd_tp.hip", "dd_vision.hip"]
+SOURCES = ["dd_dropout.hip", "dd_lm_kernels.hip", "dd_gemv.hip", "dd_attn_decode.hip", "dd_prefill.hip", "dd_engine.hip", "dd_record.hip", "dd_tp.hip", "dd_vision.hip"]
 # sources that libdropdec_tools.so takes in a second compilation with extra macros (A/B variants that must not be in the product)
 TOOLS_VARIANTS = {"dd_dropout.hip": ["-DDD_KEEP_SCRATCH_SAMPLER"],
                   # the slice GEMVs' timing experiments (dd_gemv_slices.h DD_TEXP: skipped stage-in, dropped partial sums, round-5 store

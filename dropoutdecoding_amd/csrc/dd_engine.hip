@@ -742,6 +742,7 @@ static int prefill_tail(dd_lm* h, const float* x_rows, int T0, int span_start, i
   h->tok_host[0] = 0;
   k_state_after_prefill<<<1, 64, 0, st>>>(h->state, T0, h->argmax_base, h->tokens, h->tok_host_dev);
   DD_CHECK_LAUNCH();
+  RC(dd_record_launch(&h, 1, 0, DD_REC_FIRST, st));       // record 0: the greedy first token (nothing without an attached record)
   DD_HIP(hipMemsetAsync(h->leak_bits, 0, h->Lmax, st));
   h->T_host = T0, h->span_start = span_start, h->L = L, h->n_tok_host = 1, h->prefilled = true, h->have_leak = false;
   h->last_K = 0;
@@ -1008,6 +1009,7 @@ extern "C" int dd_lm_prefill_extend(dd_lm* h, const float* embeds, int n, void* 
   h->tok_host[0] = 0;
   k_state_after_prefill<<<1, 64, 0, st>>>(h->state, pos0 + n, h->argmax_base, h->tokens, h->tok_host_dev);
   DD_CHECK_LAUNCH();
+  RC(dd_record_launch(&h, 1, 0, DD_REC_FIRST, st));
   h->T_host = pos0 + n, h->n_tok_host = 1, h->have_leak = false, h->last_K = 0, h->steps_since_prefill = 0, h->pend_valid = false;
   return DD_OK;
 }
@@ -1083,6 +1085,7 @@ extern "C" int dd_lm_prefill_ensemble(dd_lm* h, const float* embeds, int T0, int
   k_first_token_from_member<<<1, 1024, 0, st>>>(h->state, h->member_tok, h->member_logits, h->Vpad, h->last_logits,
                                                 h->tokens, h->hidden, d, h->last_hidden, h->tok_host_dev);
   DD_CHECK_LAUNCH();
+  RC(dd_record_launch(&h, 1, K, DD_REC_FIRST_ENSEMBLE, st));   // record 0 again: this time a real ensemble record
   h->last_K = K;
   return DD_OK;
 }
@@ -1194,7 +1197,8 @@ int lm_sweep(dd_lm* h, int nb, const uint8_t* bits, int row0, float* logits_out,
 // -----------------------------------------------------------------------------------------------
 // decode step, phased
 // -----------------------------------------------------------------------------------------------
-extern "C" int dd_lm_step_base(dd_lm* h, const double* mprobs, int K, dd_rng* rng, const float* uniforms, void* stream_) {
+// (the exported phase calls are wrappers further down: they refuse a handle with a generation record attached)
+static int step_base(dd_lm* h, const double* mprobs, int K, dd_rng* rng, const float* uniforms, void* stream_) {
   hipStream_t st = (hipStream_t)stream_;
   DD_REQUIRE(h, "dd_lm_step_base: null handle");
   DD_REQUIRE(h->tp_world == 1, "this handle is a tensor-parallel shard: drive it through dd_lm_tp_* (include/dropdec.h)");
@@ -1230,7 +1234,7 @@ extern "C" int dd_lm_step_base(dd_lm* h, const double* mprobs, int K, dd_rng* rn
   return DD_OK;
 }
 
-extern "C" int dd_lm_step_members(dd_lm* h, int m_lo, int m_hi, void* stream_) {
+static int step_members(dd_lm* h, int m_lo, int m_hi, void* stream_) {
   hipStream_t st = (hipStream_t)stream_;
   DD_REQUIRE(h && h->prefilled, "dd_lm_step_members: bad state");
   DD_REQUIRE(h->tp_world == 1, "this handle is a tensor-parallel shard: drive it through dd_lm_tp_* (include/dropdec.h)");
@@ -1255,12 +1259,13 @@ extern "C" int dd_lm_step_members(dd_lm* h, int m_lo, int m_hi, void* stream_) {
   return DD_OK;
 }
 
-extern "C" int dd_lm_step_commit(dd_lm* h, int K, void* stream_) {
+static int step_commit(dd_lm* h, int K, void* stream_) {
   hipStream_t st = (hipStream_t)stream_;
   DD_REQUIRE(h && h->prefilled && K == h->last_K, "dd_lm_step_commit: bad state (K=%d, expected %d)", K, h ? h->last_K : -1);
   if (K > 0) RC(vote_members(h, K, st));
   RC(ddk_commit_kv(h->commit_k ? h->commit_k : h->knew, h->commit_v ? h->commit_v : h->vnew, h->Lyr, KV_ROWS,
                    h->kv_dim, h->kc, h->vc, h->lsk, h->lsv, h->T_cap, h->state, K > 0 ? 1 : 0, st, h->kv16));
+  RC(dd_record_launch(&h, 1, K, DD_REC_STEP, st));        // after the vote, before the step's end: slot = n_tok, done == 0 = "this step emits"
   k_step_end<<<1, 1024, 0, st>>>(h->state, K, h->argmax_base, h->member_tok, h->base_logits, h->member_logits, h->Vpad,
                                  h->last_logits, h->tokens, h->drop_bits, h->L, h->leak_bits, h->cfg.leak_mask, h->hidden,
                                  h->d, h->last_hidden, h->tok_host_dev);
@@ -1270,6 +1275,21 @@ extern "C" int dd_lm_step_commit(dd_lm* h, int K, void* stream_) {
   h->pend_valid = false;       // (the rider step re-parks its ring leaders after its sweeps; every other caller leaves nothing parked)
   if (h->cfg.leak_mask && K > 0) h->have_leak = true;
   return DD_OK;
+}
+// K-shard phase calls (dist.KShardDecoder): records are not covered there — the winner's row may live on another rank until the exchange
+#define DD_NO_RECORD(h, name) \
+  DD_REQUIRE(!(h) || !(h)->rec, name ": a generation record is attached: the K-shard phase calls do not write records (include/dropdec.h)")
+extern "C" int dd_lm_step_base(dd_lm* h, const double* mprobs, int K, dd_rng* rng, const float* uniforms, void* stream_) {
+  DD_NO_RECORD(h, "dd_lm_step_base");
+  return step_base(h, mprobs, K, rng, uniforms, stream_);
+}
+extern "C" int dd_lm_step_members(dd_lm* h, int m_lo, int m_hi, void* stream_) {
+  DD_NO_RECORD(h, "dd_lm_step_members");
+  return step_members(h, m_lo, m_hi, stream_);
+}
+extern "C" int dd_lm_step_commit(dd_lm* h, int K, void* stream_) {
+  DD_NO_RECORD(h, "dd_lm_step_commit");
+  return step_commit(h, K, stream_);
 }
 
 // -----------------------------------------------------------------------------------------------
@@ -1589,7 +1609,7 @@ static int group_finish(dd_lm* h, dd_lm* const* qs, int ng, int K, hipStream_t s
   }
   if (!plain_vote) {                            // select_by_average: per sequence, as dd_lm_step_commit does it
     for (int g = 0; g < ng; ++g) {
-      RC(dd_lm_step_commit(qs[g], K, st));
+      RC(step_commit(qs[g], K, st));
       qs[g]->steps_since_prefill++;
     }
     return DD_OK;
@@ -1612,6 +1632,7 @@ static int group_finish(dd_lm* h, dd_lm* const* qs, int ng, int K, hipStream_t s
   }
   RC(dd_vote_lanes(ids, out2, gates, ng, K, st));
   RC(ddk_commit_kv_lanes(cl, ng, h->Lyr, KV_ROWS, h->kv_dim, h->T_cap, st));
+  RC(dd_record_launch(qs, ng, K, DD_REC_STEP, st));
   k_step_end_lanes<<<ng, 1024, 0, st>>>(el, K, h->Vpad);
   DD_CHECK_LAUNCH();
   for (int g = 0; g < ng; ++g) {
@@ -1987,12 +2008,12 @@ static int group_step_eager(dd_lm* const* lanes, int n, const double* mprobs, in
         m += ng - 1;
         continue;
       }
-      RC(dd_lm_step_members(q, 0, K, stream_));
+      RC(step_members(q, 0, K, stream_));
     } else {
       // stock greedy: the base row's new K/V (in the leader's scratch, row m) is what gets appended
       q->commit_k = h0->knew + (size_t)m * h0->kv_dim, q->commit_v = h0->vnew + (size_t)m * h0->kv_dim;
     }
-    int rc = dd_lm_step_commit(q, K, stream_);
+    int rc = step_commit(q, K, stream_);
     q->commit_k = q->commit_v = nullptr;
     RC(rc);
     q->steps_since_prefill++;
@@ -2161,7 +2182,7 @@ static int spec_phase_c(dd_lm* h, int K, hipStream_t st) {
     RC(dd_argmax_rows_gated(h->hidden, K, h->d, h->d, h->member_vote, gate, st));
   }
   h->last_K = K;
-  return dd_lm_step_commit(h, K, st);
+  return step_commit(h, K, st);
 }
 static int decode_step_spec(dd_lm* h, const double* mprobs, int K, dd_rng* rng, const float* uniforms, hipStream_t st) {
   RC(spec_phase_a(h, mprobs, K, rng, uniforms, st, false));
@@ -2172,9 +2193,9 @@ static int decode_step_spec(dd_lm* h, const double* mprobs, int K, dd_rng* rng, 
 static int decode_step_eager(dd_lm* h, const double* mprobs, int K, dd_rng* rng, const float* uniforms, void* stream, bool speculate) {
   if (speculate && K >= 1 && K <= 8 && h && h->prefilled && mprobs && h->T_host + 1 < h->T_cap && h->n_tok_host < MAX_NEW_TOKENS)
     return decode_step_spec(h, mprobs, K, rng, uniforms, (hipStream_t)stream);
-  RC(dd_lm_step_base(h, mprobs, K, rng, uniforms, stream));
-  if (K > 0) RC(dd_lm_step_members(h, 0, K, stream));
-  return dd_lm_step_commit(h, K, stream);
+  RC(step_base(h, mprobs, K, rng, uniforms, stream));
+  if (K > 0) RC(step_members(h, 0, K, stream));
+  return step_commit(h, K, stream);
 }
 
 

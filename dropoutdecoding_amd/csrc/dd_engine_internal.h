@@ -113,6 +113,11 @@ struct dd_lm {
   size_t tp_gather_floats = 0;
   int (*tp_exchange)(void* ctx, int rows, void* stream) = nullptr;   // one rank per process: all-gather of the slots (torch.distributed)
   void* tp_ctx = nullptr;
+  // generation record (dd_lm_set_record, dd_record.hip): the caller's ring of `rec_cap` records and, optionally, its score plane
+  void* rec = nullptr;
+  int rec_cap = 0;
+  float* rec_scores = nullptr;
+  size_t rec_scores_ld = 0;
 };
 
 #define KV_ROWS_PER_LAYER KV_ROWS
@@ -126,6 +131,14 @@ unsigned long long dd_engine_epoch();
 int dd_engine_tp_alloc(dd_lm* h, float** p, size_t floats);  // device memory owned (and released) by the handle
 // set by libdropdec_tools.so (dd_tools_trace_*): called at the end of every group_finish, on the stream of that sweep
 extern int (*dd_engine_group_finish_hook)(dd_lm* const* qs, int ng, int K, hipStream_t st);
+// generation record (dd_record.hip): one record per listed sequence, one workgroup each.  mode DD_REC_STEP: a decode step, between
+// the vote and the step's end (slot = the sequence's token count, nothing for a finished sequence); DD_REC_FIRST: slot 0 after a
+// prefill's greedy token (no ensemble); DD_REC_FIRST_ENSEMBLE: slot 0 after dd_lm_prefill_ensemble's vote.  Sequences without an
+// attached record are left out; no launch when none has one.
+#define DD_REC_STEP 0
+#define DD_REC_FIRST 1
+#define DD_REC_FIRST_ENSEMBLE 2
+int dd_record_launch(dd_lm* const* qs, int n, int K, int mode, hipStream_t st);
 // one packed sweep of nb rows through all layers + lm_head (dd_engine.hip)
 int lm_sweep(dd_lm* h, int nb, const uint8_t* bits, int row0, float* logits_out, hipStream_t st, dd_lm* const* lanes = nullptr,
              const int32_t* skip_if = nullptr);

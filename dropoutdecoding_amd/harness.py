@@ -91,9 +91,10 @@ class CaptionLog:
         if d:
             os.makedirs(d, exist_ok=True)
 
-    def append(self, image_id: int, caption: str) -> None:
+    def append(self, image_id: int, caption: str, extra: Optional[Dict] = None) -> None:
+        """extra (--token-scores): further keys of the line; without it the line is the reference's, byte for byte."""
         with open(self.path, "a") as f:                       # appended per image, so an interrupted run keeps its rows
-            json.dump({"image_id": int(image_id), "caption": caption}, f)
+            json.dump({"image_id": int(image_id), "caption": caption, **(extra or {})}, f)
             f.write("\n")
 
 
@@ -128,6 +129,20 @@ def load_sampled_ids(path: str) -> List[int]:
     return [int(line.strip()) for line in open(path) if line.strip()]          # chair_test.py:222-226
 
 
+# ---- per-token scores (opt-in; the reference would get them from HF: generate(..., return_dict_in_generate=True, output_scores=True)) ----
+def _as_list(x) -> List:
+    return x.tolist() if hasattr(x, "tolist") else list(x)
+
+
+def token_score_fields(out) -> Dict:
+    """The per-token lists a caption line gains under --token-scores, from a generate(return_dict_in_generate=True) result: the
+    winner's log-probability of every new token, how many ensemble members voted for it, and what the un-masked model gave it."""
+    rec = out["dropout_record"]
+    return {"token_logprobs": [float(v) for v in _as_list(rec["token_logprobs"])],
+            "votes": [int(v) for v in _as_list(rec["votes"])],
+            "base_token_logprobs": [float(v) for v in _as_list(rec["base_token_logprobs"])]}
+
+
 # ---- the caption loop (chair_test.py:270-372) ---------------------------------------------------------------------------
 def _caption_inputs(processor, model_name: str, image, device):
     prompt = CHAIR_PROMPTS[model_name]
@@ -140,19 +155,25 @@ def _caption_inputs(processor, model_name: str, image, device):
 
 def caption_images(model, processor, items: Iterable, model_name: str, log: CaptionLog, load_image: Callable,
                    max_new_tokens: int = 512, num_beams: int = 1, device="cuda", on_caption: Optional[Callable] = None,
-                   pipeline=None, lanes: int = 8) -> int:
+                   pipeline=None, lanes: int = 8, token_scores: bool = False) -> int:
     """items: (image_id, image_path) pairs.  Builds the inputs the way the reference does for each family, calls
     `model.generate(**inputs, max_new_tokens, num_beams, pad_token_id=eos)`, decodes, strips, filters, appends.
 
     pipeline: a `dropoutdecoding_amd.vlm.GroupPipeline` over `model` — the images are then captioned `lanes` at a time
-    (same captions per image as its own lane's generate(); rows are appended in input order)."""
+    (same captions per image as its own lane's generate(); rows are appended in input order).
+    token_scores: ask generate() for its per-token record and add `token_logprobs`, `votes`, `base_token_logprobs` to each line."""
     n = 0
+    gen_kw = {"return_dict_in_generate": True} if token_scores else {}
 
-    def finish(image_id, output_ids):
+    def finish(image_id, out):
         nonlocal n
+        output_ids = out["sequences"] if token_scores else out
         text = processor.batch_decode(output_ids, skip_special_tokens=True)[0]
         caption = filter_unk_sentences(strip_prompt_echo(model_name, text))
-        log.append(image_id, caption)
+        if token_scores:
+            log.append(image_id, caption, token_score_fields(out))
+        else:
+            log.append(image_id, caption)
         if on_caption:
             on_caption(image_id, caption)
         n += 1
@@ -161,7 +182,7 @@ def caption_images(model, processor, items: Iterable, model_name: str, log: Capt
         for image_id, path in items:
             inputs = _caption_inputs(processor, model_name, load_image(path), device)
             finish(image_id, model.generate(**inputs, max_new_tokens=max_new_tokens, num_beams=num_beams,
-                                            pad_token_id=processor.tokenizer.eos_token_id))  # chair_test.py:337-342
+                                            pad_token_id=processor.tokenizer.eos_token_id, **gen_kw))  # chair_test.py:337-342
         return n
     if num_beams != 1:
         raise ValueError("the grouped path is greedy (num_beams=1), like the dropout-decoding path itself")
@@ -172,7 +193,7 @@ def caption_images(model, processor, items: Iterable, model_name: str, log: Capt
         for b in range(0, len(items), lanes):
             yield [dict(_caption_inputs(processor, model_name, load_image(path), device)) for _, path in items[b:b + lanes]]
     for ids, outs in zip(ids_of, pipeline.run(batches(), max_new_tokens=max_new_tokens,
-                                              eos_token_id=getattr(model, "eos_token_ids", None) or None)):
+                                              eos_token_id=getattr(model, "eos_token_ids", None) or None, **gen_kw)):
         for image_id, out in zip(ids, outs):
             finish(image_id, out)
     return n
@@ -223,15 +244,17 @@ def pope_scores(answers: Sequence[str], labels: Sequence[str], number: Optional[
 
 def write_pope_answers(path: str, rows: Sequence[Dict]) -> None:
     with open(path, "w") as f:                                 # {"question", "answer"} per line, pope_test.py:72-77,243-246
-        for r in rows:
-            f.write(json.dumps({"question": r["question"], "answer": r["answer"]}) + "\n")
+        for r in rows:                                         # (+ the answer token's scores where answer_pope(token_scores=True) added them)
+            f.write(json.dumps({"question": r["question"], "answer": r["answer"],
+                                **{k: r[k] for k in ("logprob", "base_logprob") if k in r}}) + "\n")
 
 
 def answer_pope(model, processor, questions: Sequence[Dict], model_name: str, image_root: str, load_image: Callable,
-                number: Optional[int] = None, device="cuda", reuse_image_prefix: bool = False) -> List[Dict]:
+                number: Optional[int] = None, device="cuda", reuse_image_prefix: bool = False, token_scores: bool = False) -> List[Dict]:
     """pope_test.py:215-241: one generated token per question.  reuse_image_prefix: POPE asks several questions per image
     back to back; with it the image prefix (vision tower, its prefill, uncertainty) is computed once per image and only
-    the question text is prefilled for the others — same answers (settings['reuse_image_prefix'], LLaVA families)."""
+    the question text is prefilled for the others — same answers (settings['reuse_image_prefix'], LLaVA families).
+    token_scores: each row also carries the answer token's `logprob` and `base_logprob` (what the un-masked model gave it)."""
     rows = []
     if reuse_image_prefix:
         settings["reuse_image_prefix"] = True
@@ -239,9 +262,16 @@ def answer_pope(model, processor, questions: Sequence[Dict], model_name: str, im
         image = load_image(os.path.join(image_root, q["image"]))
         inputs = processor(text=pope_prompt(model_name, q["text"]), images=image, return_tensors="pt")
         inputs = inputs.to(device) if hasattr(inputs, "to") else inputs
-        out = model.generate(**inputs, max_new_tokens=1, num_beams=1, pad_token_id=processor.tokenizer.eos_token_id)
+        if token_scores:
+            res = model.generate(**inputs, max_new_tokens=1, num_beams=1, pad_token_id=processor.tokenizer.eos_token_id,
+                                 return_dict_in_generate=True)
+            out, sc = res["sequences"], token_score_fields(res)
+        else:
+            out = model.generate(**inputs, max_new_tokens=1, num_beams=1, pad_token_id=processor.tokenizer.eos_token_id)
         text = processor.batch_decode(out, skip_special_tokens=True)[0]
         rows.append({"question": q["text"], "answer": strip_prompt_echo(model_name, text)})
+        if token_scores:
+            rows[-1].update(logprob=sc["token_logprobs"][0], base_logprob=sc["base_token_logprobs"][0])
     return rows
 
 
@@ -270,6 +300,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--max-new-tokens", type=int, default=512)
     p.add_argument("--lanes", type=int, default=1,
                    help="images captioned concurrently on the GPU (1 = the reference's one-at-a-time loop; up to 16)")
+    p.add_argument("--token-scores", action="store_true", default=False,
+                   help="add per-token token_logprobs / votes / base_token_logprobs lists to every caption line (default: off, "
+                        "the lines are the reference's)")
     return p
 
 
@@ -302,7 +335,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         pipe = GroupPipeline(model, lanes=args.lanes)
     n = caption_images(model, processor, items, args.model, log, lambda p: Image.open(p).convert("RGB"),
                        max_new_tokens=args.max_new_tokens, num_beams=args.num_beams or 1,
-                       on_caption=lambda i, c: print(c), pipeline=pipe, lanes=max(1, args.lanes))
+                       on_caption=lambda i, c: print(c), pipeline=pipe, lanes=max(1, args.lanes), token_scores=args.token_scores)
     print("the result is saved into", args.output_dir, name, f"({n} captions)")
     return 0
 

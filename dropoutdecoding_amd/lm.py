@@ -171,6 +171,7 @@ class DropoutEngine:
         self._n_enqueued = 0
         self._eos_dev: Optional[tuple] = None        # eos ids currently held in the sequence's device state
         self.sync_steps = True                       # generate(): host-decided fallback of the speculative step
+        self._rec_buf, self._rec_scores, self._rec_cap = None, None, 0     # generation record (attach_record)
 
     def _s(self) -> int:
         return self.torch_stream.cuda_stream
@@ -373,6 +374,64 @@ class DropoutEngine:
         arr = (C.c_int32 * max(len(ids), 1))(*ids)
         self._ck(self.lib.dd_lm_set_eos(self._h, arr, len(ids), self._s()), "dd_lm_set_eos")
         self._eos_dev = ids
+
+    # ---- generation record (include/dropdec.h "Generation record") ------------------------------
+    def attach_record(self, capacity: int, scores: bool = False, keep: bool = False) -> None:
+        """Have every emitted token leave a record on the device (dd_lm_set_record): the vote, masked_numbers, the winner's and the
+        un-masked pass' softmax summary and, with scores=True, the full score row (HF's `scores`).  `capacity` records, slot 0 =
+        the prefill's token; attach before the prefill.  The step writes them itself, so nothing synchronises; read with record().
+        Every call attaches fresh buffers, so tensors handed out by record() earlier stay what they were.  keep=True (GroupPipeline,
+        which copies the records out after every batch) keeps a ring of the same capacity and kind that is already attached — its
+        slots are written again from slot 0 by the next prefill: no call into the library, no new step graphs."""
+        if capacity < 1:
+            raise ValueError("attach_record: capacity must be at least 1")
+        if keep and self._rec_buf is not None and self._rec_cap == int(capacity) and (self._rec_scores is not None) == bool(scores):
+            return
+        self.detach_record()
+        nbytes = _lib.record_dtype().itemsize
+        # uninitialised: record() hands out the written slots only.  Allocated on the caller's current stream, the one the prefill
+        # that follows is ordered after (prefill() waits for it; GroupPipeline attaches on its prefill stream)
+        rec = torch.empty(capacity, nbytes, dtype=torch.uint8, device=self.device)
+        sc = torch.empty(capacity, self.cfg.vocab_size, dtype=torch.float32, device=self.device) if scores else None
+        self._ck(self.lib.dd_lm_set_record(self._h, rec.data_ptr(), int(capacity), sc.data_ptr() if sc is not None else None,
+                                             self.cfg.vocab_size if sc is not None else 0, self._s()), "dd_lm_set_record")
+        self._rec_buf, self._rec_scores, self._rec_cap = rec, sc, int(capacity)
+
+    def detach_record(self) -> None:
+        """Stop recording; tensors handed out by record() stay valid (they keep the buffers alive)."""
+        if getattr(self, "_rec_buf", None) is not None:
+            self.torch_stream.synchronize()                  # steps still in flight write into the ring
+            self._ck(self.lib.dd_lm_set_record(self._h, None, 0, None, 0, self._s()), "dd_lm_set_record")
+        self._rec_buf, self._rec_scores, self._rec_cap = None, None, 0
+
+    def record(self) -> Dict[str, torch.Tensor]:
+        """The records of the tokens emitted so far (synchronises): torch views of the device buffers, one row per token.
+        Keys: tokens, winner, votes, base_tokens, member_tokens [n, K], masked_numbers [n, K], token_logprobs, base_token_logprobs,
+        entropy, top_ids [n, 8], top_logprobs [n, 8] (= top_logits - lse), scores [n, V] when attached with scores=True — and the
+        raw columns they are made of: K, max_logit, lse, top_logits, and `raw`, the records' bytes [n, dd_record_bytes()]."""
+        if getattr(self, "_rec_buf", None) is None:
+            raise _lib.DDError("record(): no generation record attached (attach_record)")
+        n = max(0, min(self.n_tokens(), self._rec_cap))
+        dt = _lib.record_dtype()
+        raw = self._rec_buf[:n]
+        i32, f32 = raw.view(torch.int32), raw.view(torch.float32)
+
+        def col(name):
+            fmt, off = dt.fields[name][0], dt.fields[name][1] // 4
+            cnt = fmt.shape[0] if fmt.shape else 1
+            src = f32 if fmt.base == np.float32 else i32
+            return src[:, off] if not fmt.shape else src[:, off:off + cnt]
+
+        K = int(col("K").max()) if n else 0
+        lse = col("lse")
+        out = {"tokens": col("token"), "winner": col("winner"), "votes": col("votes"), "K": col("K"), "base_tokens": col("base_token"),
+               "member_tokens": col("member_token")[:, :K], "masked_numbers": col("n_drop")[:, :K],
+               "token_logprobs": col("logprob"), "base_token_logprobs": col("base_logprob"), "entropy": col("entropy"),
+               "max_logit": col("max"), "lse": lse, "top_ids": col("top_id"), "top_logits": col("top_logit"),
+               "top_logprobs": col("top_logit") - lse[:, None], "raw": raw}
+        if self._rec_scores is not None:
+            out["scores"] = self._rec_scores[:n]
+        return out
 
     def set_next_token(self, token: int) -> None:
         self._ck(self.lib.dd_lm_set_next_token(self._h, int(token), self._s()), "dd_lm_set_next_token")

@@ -40,6 +40,40 @@ def lm_state_dict_from_hf(hf_model) -> Dict[str, torch.Tensor]:
     return out
 
 
+class DropoutGenerateOutput(dict):
+    """What generate(..., return_dict_in_generate=True) returns — the fields of HF's GenerateDecoderOnlyOutput this path has,
+    with attribute and item access as on HF's ModelOutput (the reference's generate() is HF's: chair_test/chair_test.py:341-346):
+    `sequences` (the tensor the plain call returns), `scores` / `logits` (a tuple of [1, V] views of the device's score plane,
+    one per new token; None unless asked for; the path has no logits processors, so both are the same rows) and
+    `dropout_record` (DropoutEngine.record(): the vote, masked_numbers and softmax summaries of every token)."""
+
+    def __init__(self, sequences=None, scores=None, logits=None, dropout_record=None):
+        super().__init__(sequences=sequences, scores=scores, logits=logits, dropout_record=dropout_record)
+
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name) from None
+
+    def __setattr__(self, name, value):
+        self[name] = value
+
+    def __getitem__(self, k):
+        if isinstance(k, str):
+            return dict.__getitem__(self, k)
+        return self.to_tuple()[k]                       # ModelOutput: integer / slice access skips the None fields
+
+    def to_tuple(self):
+        return tuple(v for v in self.values() if v is not None)
+
+
+def _resolve_new_tokens(input_ids, max_new_tokens, max_length) -> int:
+    if max_new_tokens is None:
+        max_new_tokens = 20 if max_length is None else max(1, max_length - input_ids.shape[1])
+    return int(max_new_tokens)
+
+
 class DropoutVLM:
     """Base of the drop-in wrappers.  One model object = one in-flight sequence (as in the reference)."""
 
@@ -122,8 +156,7 @@ class DropoutVLM:
                              "(reference models/llava.py:75-76)")
         if num_beams != 1 or do_sample:
             raise ValueError("the dropout-decoding path is greedy (num_beams=1, do_sample=False)")
-        if max_new_tokens is None:
-            max_new_tokens = 20 if max_length is None else max(1, max_length - input_ids.shape[1])
+        max_new_tokens = _resolve_new_tokens(input_ids, max_new_tokens, max_length)
         input_ids = input_ids.to(self.device)
         # the `# if True:` toggle of llava.py:336-337; never for the stock greedy (`--original`) path
         first = bool(settings.get("first_step_ensemble", False)) and not self.original
@@ -198,14 +231,52 @@ class DropoutVLM:
         new = torch.tensor([toks], dtype=torch.long, device=input_ids.device)
         return self._format_output(input_ids, new)
 
+    # ---- per-token scores and the ensemble record (return_dict_in_generate) -------------------
+    def _record_begin(self, input_ids, max_new_tokens, max_length, want_scores: bool, keep: bool = False) -> None:
+        """Attach a ring of max_new_tokens records (and the score plane) BEFORE the prefill: record 0 is the prefill's token."""
+        if input_ids is None:
+            return                                       # _prepare raises the reference's error
+        self.engine.attach_record(_resolve_new_tokens(input_ids, max_new_tokens, max_length), scores=want_scores, keep=keep)
+
+    def _record_end(self, sequences, output_scores: bool, output_logits: bool, copy: bool = False) -> DropoutGenerateOutput:
+        """Read the ring after the loop (the loop itself gained no host sync) and hand its buffers over to the result — or, with
+        copy=True, copy the written slots out and keep the ring attached for the lane's next image (GroupPipeline)."""
+        rec = self.engine.record()
+        if copy:
+            rec = {k: v.clone() for k, v in rec.items()}
+            # the ring is written again by this lane's next prefill, on another stream: that prefill waits for the copies (_stage)
+            self._rec_copied = torch.cuda.Event()
+            self._rec_copied.record(torch.cuda.current_stream(self.device))
+        else:
+            self.engine.detach_record()
+        rows = None
+        if "scores" in rec:
+            sc = rec["scores"]
+            rows = tuple(sc[i:i + 1] for i in range(sc.shape[0]))
+        return DropoutGenerateOutput(sequences=sequences, scores=rows if output_scores else None,
+                                     logits=rows if output_logits else None, dropout_record=rec)
+
     @torch.no_grad()
     def generate(self, input_ids: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
                  max_new_tokens: Optional[int] = None, max_length: Optional[int] = None, num_beams: int = 1,
-                 pad_token_id: Optional[int] = None, eos_token_id=None, do_sample: bool = False, **inputs) -> torch.LongTensor:
-        input_ids, max_new_tokens, eos = self._prepare(input_ids, max_new_tokens, max_length, num_beams, eos_token_id,
-                                                       do_sample, inputs)
-        toks = self._decode_loop(max_new_tokens, eos)
-        return self._finalize(input_ids, toks)
+                 pad_token_id: Optional[int] = None, eos_token_id=None, do_sample: bool = False,
+                 return_dict_in_generate: bool = False, output_scores: bool = False, output_logits: bool = False, **inputs):
+        """With return_dict_in_generate=False: the id tensor, exactly as before (output_scores / output_logits are ignored, as HF
+        does).  With it: a DropoutGenerateOutput."""
+        if not return_dict_in_generate:
+            input_ids, max_new_tokens, eos = self._prepare(input_ids, max_new_tokens, max_length, num_beams, eos_token_id,
+                                                           do_sample, inputs)
+            toks = self._decode_loop(max_new_tokens, eos)
+            return self._finalize(input_ids, toks)
+        self._record_begin(input_ids, max_new_tokens, max_length, output_scores or output_logits)
+        try:
+            input_ids, max_new_tokens, eos = self._prepare(input_ids, max_new_tokens, max_length, num_beams, eos_token_id,
+                                                           do_sample, inputs)
+            toks = self._decode_loop(max_new_tokens, eos)
+            seq = self._finalize(input_ids, toks)
+            return self._record_end(seq, output_scores, output_logits)
+        finally:
+            self.engine.detach_record()
 
     # ---- several images at once (lanes) ---------------------------------------------------------
     def spawn_lane(self) -> "DropoutVLM":
@@ -334,34 +405,47 @@ def prefill_lanes(models: List["DropoutVLM"], stream=None, chunk: int = 16) -> N
 
 @torch.no_grad()
 def generate_group(models: List[DropoutVLM], inputs: List[dict], max_new_tokens: Optional[int] = None, eos_token_id=None,
-                   num_beams: int = 1, do_sample: bool = False, pad_token_id: Optional[int] = None) -> List[torch.LongTensor]:
+                   num_beams: int = 1, do_sample: bool = False, pad_token_id: Optional[int] = None,
+                   return_dict_in_generate: bool = False, output_scores: bool = False, output_logits: bool = False) -> List:
     """`generate()` for up to 64 images at once: models[i] (a wrapper and its spawn_lane() copies) decodes inputs[i].
 
     Each image is decoded exactly as `models[i].generate(**inputs[i])` would (same tokens, masks, logits; its own rng
     stream, like one process of the reference's sharded 500-image runs), but all sequences advance together and their
-    un-masked passes share one sweep over the weights (EngineGroup) — the throughput mode for CHAIR-style jobs."""
+    un-masked passes share one sweep over the weights (EngineGroup) — the throughput mode for CHAIR-style jobs.
+    return_dict_in_generate / output_scores / output_logits as in generate(): one DropoutGenerateOutput per image."""
     from .lm import EngineGroup
     if len(models) != len(inputs) or not 1 <= len(models) <= 64:
         raise ValueError("generate_group: one model lane per input, 1..64 of them")
     prepared = []
     visuals = _batched_visuals(models[0], inputs)
-    for m, kw, vis in zip(models, inputs, visuals):
-        kw = dict(kw)
-        kw.pop("attention_mask", None)
-        ids = kw.pop("input_ids", None)
-        mnt = kw.pop("max_new_tokens", max_new_tokens)
-        prepared.append(m._prepare(ids, mnt, kw.pop("max_length", None), num_beams, kw.pop("eos_token_id", eos_token_id),
-                                   do_sample, kw, defer_prefill=True, visual=vis))
-    prefill_lanes(models)
-    n_new = {p[1] for p in prepared}
-    eos = prepared[0][2]
-    if len(n_new) != 1 or any(p[2] != eos for p in prepared):
-        raise ValueError("generate_group: all images of a group share max_new_tokens and eos_token_id")
-    dropout = {not m.original for m in models}
-    if len(dropout) != 1:
-        raise ValueError("generate_group: `original` must be the same for all lanes")
-    toks = EngineGroup([m.engine for m in models]).generate(n_new.pop(), eos=eos, dropout=dropout.pop())
-    return [m._finalize(p[0], t) for m, p, t in zip(models, prepared, toks)]
+    try:
+        for m, kw, vis in zip(models, inputs, visuals):
+            kw = dict(kw)
+            kw.pop("attention_mask", None)
+            ids = kw.pop("input_ids", None)
+            mnt = kw.pop("max_new_tokens", max_new_tokens)
+            mlen = kw.pop("max_length", None)
+            if return_dict_in_generate:
+                m._record_begin(ids, mnt, mlen, output_scores or output_logits)
+            prepared.append(m._prepare(ids, mnt, mlen, num_beams, kw.pop("eos_token_id", eos_token_id),
+                                       do_sample, kw, defer_prefill=True, visual=vis))
+        prefill_lanes(models)
+        n_new = {p[1] for p in prepared}
+        eos = prepared[0][2]
+        if len(n_new) != 1 or any(p[2] != eos for p in prepared):
+            raise ValueError("generate_group: all images of a group share max_new_tokens and eos_token_id")
+        dropout = {not m.original for m in models}
+        if len(dropout) != 1:
+            raise ValueError("generate_group: `original` must be the same for all lanes")
+        toks = EngineGroup([m.engine for m in models]).generate(n_new.pop(), eos=eos, dropout=dropout.pop())
+        seqs = [m._finalize(p[0], t) for m, p, t in zip(models, prepared, toks)]
+        if not return_dict_in_generate:
+            return seqs
+        return [m._record_end(sq, output_scores, output_logits) for m, sq in zip(models, seqs)]
+    finally:
+        if return_dict_in_generate:
+            for m in models:
+                m.engine.detach_record()
 
 
 class GroupPipeline:
@@ -385,6 +469,17 @@ class GroupPipeline:
     def _stage(self, lanes, batch, kw):
         """-> per-image closures that each enqueue one image's front-end + prefill on the second stream"""
         state = {"prepared": [], "todo": list(zip(lanes, batch)), "event": None, "lanes": lanes[:len(batch)], "staged": [], "vis": []}
+        if kw.get("return_dict_in_generate"):
+            # rings before the batch's prefills (record 0 is the prefill's token), allocated on the stream those run on.  A lane keeps its
+            # ring from batch to batch (its previous batch's records were copied out in run()): after a lane's first batch nothing is
+            # attached, so the other set's decode keeps replaying its step graph
+            with torch.cuda.stream(self.pre_stream):
+                for m, inp in zip(lanes, batch):
+                    if getattr(m, "_rec_copied", None) is not None:
+                        self.pre_stream.wait_event(m._rec_copied)
+                        m._rec_copied = None
+                    m._record_begin(inp.get("input_ids"), inp.get("max_new_tokens", kw["max_new_tokens"]), inp.get("max_length"),
+                                    kw.get("output_scores") or kw.get("output_logits"), keep=True)
 
         def unit() -> bool:
             if not state["todo"]:
@@ -414,17 +509,30 @@ class GroupPipeline:
         return state
 
     @torch.no_grad()
-    def run(self, batches, max_new_tokens: int, eos_token_id=None):
+    def run(self, batches, max_new_tokens: int, eos_token_id=None, return_dict_in_generate: bool = False, output_scores: bool = False,
+            output_logits: bool = False):
         """batches: iterable of lists of generate() keyword dicts (up to `lanes` each); yields the list of output id tensors
-        of each batch, in order."""
+        of each batch, in order — with return_dict_in_generate, of DropoutGenerateOutput objects as generate() returns them (each
+        batch's records are copied out of the lanes' rings before those lanes are used again two batches later)."""
         from .lm import EngineGroup
-        kw = {"max_new_tokens": max_new_tokens, "eos_token_id": eos_token_id}
+        kw = {"max_new_tokens": max_new_tokens, "eos_token_id": eos_token_id, "return_dict_in_generate": return_dict_in_generate,
+              "output_scores": output_scores, "output_logits": output_logits}
         it = iter(batches)
         first = next(it, None)
         while first is not None and len(first) == 0:           # empty batches (a trailing [] of a batching generator) are skipped
             first = next(it, None)
         if first is not None and len(first) > len(self.sets[0]):
             raise ValueError(f"a batch of {len(first)} images for {len(self.sets[0])} lanes")
+        try:
+            yield from self._run(it, first, kw)
+        finally:
+            if return_dict_in_generate:                # also when the caller's iterator or a batch raised: no ring stays attached
+                for m in self.sets[0] + self.sets[1]:
+                    m.engine.detach_record()
+
+    def _run(self, it, first, kw):
+        from .lm import EngineGroup
+        return_dict_in_generate, output_scores, output_logits = kw["return_dict_in_generate"], kw["output_scores"], kw["output_logits"]
         cur = self._stage(self.sets[0], first, kw) if first is not None else None
         k = 0
         while cur is not None:
@@ -457,5 +565,8 @@ class GroupPipeline:
             if not following["asked"]:
                 fetch()
             nxt = following["state"]
-            yield [m._finalize(p[0], t) for m, p, t in zip(lanes, prepared, toks)]
+            outs = [m._finalize(p[0], t) for m, p, t in zip(lanes, prepared, toks)]
+            if return_dict_in_generate:
+                outs = [m._record_end(sq, output_scores, output_logits, copy=True) for m, sq in zip(lanes, outs)]
+            yield outs
             cur = nxt

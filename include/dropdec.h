@@ -351,6 +351,45 @@ int dd_lm_get(dd_lm* h, int what, void* dst_host, size_t bytes, void* stream);
  * how many; does not synchronise any stream. */
 int dd_lm_peek_tokens(dd_lm* h, int32_t* dst_host, int max_tokens);
 
+/* ------------------------------------------------------------------------------------------
+ * Generation record: what the ensemble decided about every emitted token, kept on the device.
+ * The reference hands this to its callers for free: its generate() is HF's, so generate(..., return_dict_in_generate=True,
+ * output_scores=True) (the call at chair_test/chair_test.py:341-346) returns one [1, V] score row per new token, and every
+ * forward() leaves masked_numbers behind (models/llava.py:661-662).  Here decode steps are enqueued ahead of the host, so
+ * the step itself writes one fixed-size record per emitted token into a ring the caller attached:
+ *   rec_dev     `capacity` records of dd_record_bytes() bytes each (layout: dd_record_field); slot i = token i of the
+ *               sequence, slot 0 = the prefill's first token; a token beyond `capacity` is not recorded
+ *   scores_dev  optional [capacity][scores_ld] fp32 (scores_ld >= V): row i = the V unprocessed logits token i was taken
+ *               from (the winner's, models/llava.py:361-376) — HF's `scores` and `logits` alike, there are no processors
+ * Fields, 4 bytes each (int32 unless noted):
+ *   token                        the emitted id
+ *   winner, votes, K             select_by_vote (models/llava.py:22-36): winning member, members whose id equals the voted
+ *                                id, members of the step; winner = -1 and K = 0 for a step without ensemble (K = 0, or
+ *                                the prefill's greedy first token)
+ *   base_token                   argmax of the un-masked pass (models/llava.py:294-305)
+ *   member_token[64]             the id each member voted with (DD_GET_MEMBER_ARGMAX), -1 beyond K
+ *                                (DD_VOTE_AVERAGE, models/llava.py:37-52: there is no vote — entry 0 is the argmax of the members' mean, the
+ *                                emitted token, entries 1.. the members' own argmax ids; winner = 0 and votes counts the entries equal to
+ *                                the emitted token)
+ *   n_drop[64]                   masked_numbers (models/llava.py:661-662), 0 beyond K
+ *   max, lse (fp32)              max logit and max + log sum exp(x - max) of the winner's row (models/llava.py:361-376)
+ *   logprob, entropy (fp32)      x[token] - lse and -sum p log p (nats) of the winner's row (a column at -inf counts as p log p = 0)
+ *   base_logprob (fp32)          x_base[token] - lse_base: what the un-masked model gave the emitted token
+ *   top_id[8], top_logit[8]      the eight largest entries of the winner's row, descending, equal values: lowest id first
+ * One extra launch per step (one workgroup per sequence) after the vote and before the step's end; it only reads what the
+ * step computed.  A step enqueued past an EOS writes nothing.  The slot index is the sequence's token count, so every
+ * prefill and dd_lm_truncate start again at slot 0.  Every reduction runs in a fixed order: a sequence's records are the
+ * same bytes alone, as a lane of a group step, eager or replayed from a graph, and under every speculation policy.
+ * The buffers stay the caller's; rec_dev == NULL detaches.  Attaching and detaching start new step graphs (a step captured
+ * without the launch is never replayed with it); with nothing attached no launch is enqueued.
+ * Not covered: handles of a tensor-parallel rank (dd_lm_tp_*) refuse dd_lm_set_record, and the K-shard phase calls
+ * (dd_lm_step_base / _members / _commit) refuse a handle with a record attached — both with DD_EINVAL.
+ * dd_record_field: field i of the layout (host only, no GPU): name, byte offset, element count, 1 = fp32 / 0 = int32;
+ * returns DD_EINVAL past the last field. */
+int dd_lm_set_record(dd_lm* h, void* rec_dev, int capacity, float* scores_dev, size_t scores_ld, void* stream);
+size_t dd_record_bytes(void);
+int dd_record_field(int i, const char** name, int* offset, int* count, int* is_float);
+
 /* End of sequence, device-side.  HF's greedy loop (third-party GenerationMixin._sample, the caller of the reference's
  * forward(); chair_test/chair_test.py:341-346) stops at the first EOS id, and the reference's global rng stream then
  * continues into the next image (models/llava.py:16-20, :650).  Decode steps are enqueued here without host
