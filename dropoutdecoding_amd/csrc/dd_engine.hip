@@ -2711,7 +2711,8 @@ extern "C" double dd_lm_step_algorithmic_bytes(const dd_lm* h, int K) {
 // 8 = replay decode steps from hipGraphs (default 1), 11 = short prompt chunks through the decode GEMVs (default 1),
 // 13 = slice-resident 16 / 32 / 64-row GEMVs (default 1; 0: the K-split-over-waves kernels, same bits), 14 = process default of the
 // speculation policy (dd_lm_set_speculation), 15 / 16 = block order / big-block threshold of the prefill GEMM (same bits),
-// 20 = form of that big block (1: LDS-DMA 160 x 512, the default; 0: the register-staged 128 x 512 block of round 3; same bits).
+// 20 = form of that big block (1: LDS-DMA, 160 x 512 or 128 x 512 per launch, the default; 10 / 8: always that LDS-DMA block;
+// 0: the register-staged 128 x 512 block of round 3; same bits).
 extern "C" int dd_set_tuning(int key, int value) {
   dd_engine_bump_epoch();
   DD_REQUIRE(key == 8 || key == 11 || (key >= 13 && key <= 16) || key == 20, "dd_set_tuning: unknown key %d (8, 11, 13, 14, 15, 16, 20)", key);

@@ -552,8 +552,10 @@ int dd_qformer_forward(dd_qformer* h, const int32_t* text_ids_dev, int n_text, c
  *   14 process default of the speculation policy of single-sequence steps (dd_lm_set_speculation: 0 never, 1 always,
  *      2 adaptive = default),
  *   15 XCD-aware block order of the prefill GEMM (default 1; same bits), 16 rows from which the prefill GEMM uses its
- *      big LDS-staged block (default 1024; 0: never; same bits), 20 form of that block (default 1: 160 x 512, operand
- *      fragments by LDS-DMA; 0: round 3's register-staged 128 x 512 block; same bits).
+ *      big LDS-staged block (default 1024; 0: never; same bits), 20 form of that block (default 1: operand fragments by
+ *      LDS-DMA, 160 x 512 or 128 x 512 per launch, whichever needs fewer rounds of workgroups; 10 / 8: always the
+ *      160-row / the 128-row LDS-DMA block; 0: round 3's register-staged 128 x 512 block; any other value counts as 1;
+ *      same bits).
  * Kernel-variant experiment knobs and the timing hooks of bench.py / tools/ are not part of this library: they live in
  * libdropdec_tools.so (include/dropdec_tools.h). */
 int dd_set_tuning(int key, int value);

@@ -10,10 +10,17 @@ V = 2048) carry seeded `random_weights` through `load_state_dict`, and EVERY lan
   token ids, keep sets, mask flags, masked counts, member argmax ids, winner   exact
   winner's logits, un-masked logits                                            <= 1e-3 of max |logit| (north star)
 
-A discrete result may only differ where the oracle itself says the decision sits inside the logits tolerance (top-1 minus
-top-2 of the argmax in question < 1e-3 of max |logit|, or a uniform closer to its threshold than the two sides' fp32
-uncertainties move that threshold — at least the 1e-5 of test_mid_scale_llava_shapes_vs_oracle); such a lane leaves the comparison from that step on, the test reports it and fails
-if more than one lane in eight does.  (The streams are seeded, so a given tree either has such a flip or not — no flake.)
+A discrete result may only differ where the oracle itself puts the decision AT THE ELEMENT THAT DIFFERS inside the logits tolerance
+(tests/lane_check.py states the rule per kind of result): a keep-set row whose top-k ids differ at a boundary gap < 1e-3, or else a
+top-1 minus top-2 of the un-masked logits < 1e-3 of max |logit|; at every (member, token) whose mask flag differs, a uniform closer to
+its drop probability than the two sides' fp32 uncertainties move that probability (at least the 1e-5 of
+test_mid_scale_llava_shapes_vs_oracle; InstructBLIP: that token's uncertainty against that member's quantile threshold); for every
+member whose argmax id differs, that member's own top-1 minus top-2 < 1e-3.  Such a lane leaves the comparison from that step on; the
+test prints it, emits it as a warning (so that a `pytest -q` log carries it) and fails if more than one lane in eight does.  (The
+streams are seeded, so a given tree either has such a flip or not — no flake.)
+
+The batched prefill (dd_lm_prefill_group: >= 1024 rows, the large-block GEMM in each of its forms) is anchored here too:
+test_batched_prefill_7b_widths_every_form_every_lane_vs_oracle.
 """
 import numpy as np
 import pytest
@@ -24,9 +31,10 @@ pytestmark = pytest.mark.gpu
 from oracle.decode_ref import FAMILY_IBLIP, FAMILY_LLAVA, FAMILY_NEXT, RefDecoder
 from oracle.lm_ref import LMConfig as RefCfg, random_weights
 
+from lane_check import TOL, LaneCheck, report as _report          # tests/lane_check.py
+
 K8 = [0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8]
 K4 = [0.1, 0.3, 0.5, 0.7]             # the reference's shipped LLaVA-1.5 list (chair_test/chair_test.py:170)
-TOL = 1e-3                            # logits: relative to the largest |logit| (BASELINE north_star)
 STD = 0.012                           # d = 4096: q.k / sqrt(128) of a few units, logits of order one
 
 
@@ -50,17 +58,6 @@ def mistral_w():
     return dims, random_weights(RefCfg(*dims), 63, STD)
 
 
-def _relerr(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / np.abs(b).max())
-
-
-def _top_gap(v):
-    v = np.asarray(v, np.float64)
-    t = np.partition(v, -2)[-2:]
-    return float((t[1] - t[0]) / np.abs(v).max())
-
-
 def _oracle_lanes(family, rc, w, probs, embs, spans, n_new, seed0=50):
     import time
     t0 = time.time()
@@ -73,107 +70,12 @@ def _oracle_lanes(family, rc, w, probs, embs, spans, n_new, seed0=50):
     return refs
 
 
-def _thresholds(epi, probs):
-    """drop probabilities of models/llava.py:641-647 in float64: p = 0.1 + (mprob - 0.1) (e - lo) / (hi - lo)"""
-    e = np.asarray(epi, np.float64)
-    return 0.1 + (np.asarray(probs, np.float64)[:, None] - 0.1) * ((e - e.min()) / np.ptp(e))[None]
-
-
-def _mask_margin(r, ref, probs):
-    if r.uniforms is None:            # InstructBLIP: drop where e >= quantile(e, 1 - p) (instructblip.py:450-453): how close an uncertainty sits to a threshold
-        e = ref.epi.numpy().astype(np.float64)
-        thr = np.quantile(e, 1.0 - np.asarray(probs, np.float64))
-        d = np.abs(e[None, :] - thr[:, None])
-        d[d == 0.0] = np.inf          # (a threshold that IS an element — weight 0 of the interpolation — is the same element on both sides)
-        return float(d.min() / np.ptp(e))
-    return float(np.abs(r.uniforms - _thresholds(ref.epi.numpy(), probs)).min())
-
-
-class LaneCheck:
-    """One lane's step-by-step comparison with its oracle; `live` turns False at an excused near-tie."""
-
-    def __init__(self, name, eng, ref, probs):
-        self.name, self.eng, self.ref, self.probs = name, eng, ref, probs
-        self.live, self.excuse, self.worst = True, None, 0.0
-        self.topk_note = None           # the image span's top-k id sets differ at a near-tie: only the keep sets can feel it
-        self.p_limit = 1e-5             # a uniform this close to its threshold may flip (set from the two sides' uncertainties in prefill())
-
-    def _discrete(self, what, got, want, margin, limit, s):
-        if np.array_equal(np.asarray(got), np.asarray(want)):
-            return True
-        info = f"{self.name} step {s}: {what} differs from the oracle; the oracle's margin at that decision is {margin:.3g}"
-        assert margin < limit, info + f" (>= {limit:g}: not a near-tie — wrong result)"
-        self.live, self.excuse = False, info
-        return False
-
-    def prefill(self):
-        e, r = self.eng, self.ref
-        err = _relerr(e.logits(), r.prefill_logits[-1].numpy())
-        assert err <= TOL, f"{self.name}: prefill logits {err:.3g}"
-        err = _relerr(e.image_logits(), r.image_logits.numpy())
-        assert err <= TOL, f"{self.name}: image-span logits {err:.3g}"
-        np.testing.assert_allclose(e.vision_uncert_dict()["epis_uncert_per_token"][0], r.epi.numpy(), rtol=5e-3, atol=1e-6,
-                                   err_msg=f"{self.name}: epistemic uncertainty")
-        img = np.sort(r.image_logits.numpy(), axis=1)[:, ::-1]
-        k = r.topk_ids.shape[1]
-        # the thresholds divide by (max - min) of the uncertainties — a few per cent of their size for these weights — so the last bits
-        # of the two sides' fp32 uncertainties move a threshold by up to p_err: a uniform closer than that to its threshold is a tie
-        p_err = float(np.abs(_thresholds(e.vision_uncert_dict()["epis_uncert_per_token"][0], self.probs) - _thresholds(r.epi.numpy(), self.probs)).max())
-        assert p_err < 2e-4, f"{self.name}: thresholds from the two sides' uncertainties differ by {p_err:.3g}"
-        self.p_limit = max(1e-5, 2 * p_err)
-        got, want = np.sort(e.topk()[1], 1), np.sort(r.topk_ids.numpy(), 1)
-        if not np.array_equal(got, want):
-            rows = np.nonzero((got != want).any(axis=1))[0]                                  # the top-k boundary (llava.py:310)
-            rgap = ((img[rows, k - 1] - img[rows, k]) / np.abs(img[rows]).max(axis=1)).max()
-            assert rgap < TOL, f"{self.name}: top-k ids of image rows {rows.tolist()} differ from the oracle, boundary gap {rgap:.3g}"
-            self.topk_note = f"top-k ids of image rows {rows.tolist()} differ at a boundary gap of {rgap:.3g}"
-
-    def step(self, s):
-        if not self.live:
-            return
-        e, r = self.eng, self.ref.records[s]
-        st = e.last_step()
-        err = _relerr(e.base_logits(), r.base_logits)
-        assert err <= TOL, f"{self.name} step {s}: un-masked logits {err:.3g}"
-        self.worst = max(self.worst, err)
-        keep_margin = 0.0 if self.topk_note else _top_gap(r.base_logits)
-        if not self._discrete("keep set (argmax of the un-masked logits in the rows' top-k ids)", st["keep"], r.keep, keep_margin, TOL, s):
-            self.excuse += f" ({self.topk_note})" if self.topk_note else ""
-            return
-        if not self._discrete("mask flags", st["drop"], r.drop, _mask_margin(r, self.ref, self.probs), self.p_limit, s):
-            return
-        assert st["masked_numbers"].tolist() == r.masked_numbers, f"{self.name} step {s}: masked counts"
-        mm = min(r.member_margin) if r.member_margin else 1.0
-        if not self._discrete("member argmax ids", st["member_argmax"], r.member_argmax, mm, TOL, s):
-            return
-        assert st["winner"] == r.winner, f"{self.name} step {s}: winner"
-        err = _relerr(e.logits(), r.logits)
-        assert err <= TOL, f"{self.name} step {s}: winner's logits {err:.3g}"
-        self.worst = max(self.worst, err)
-
-    def tokens(self):
-        if self.live:
-            assert self.eng.tokens() == self.ref.tokens_out, f"{self.name}: token ids"
-
-
-def _report(checks, what):
-    gone = [c for c in checks if not c.live]
-    print(f"\n{what}: {len(checks) - len(gone)} of {len(checks)} lanes compared to the end, worst logits error "
-          f"{max(c.worst for c in checks):.2e} (tolerance {TOL:g})")
-    for c in gone:
-        print("  excused:", c.excuse)
-    for c in checks:
-        if c.topk_note and c.live:
-            print(f"  note: {c.name}: {c.topk_note}; no keep set felt it")
-    assert len(gone) * 8 <= len(checks), f"{what}: {len(gone)} lanes left the comparison at near-ties"
-
-
-def _lanes(E, cfg, n, family, max_visual, **kw):
+def _lanes(E, cfg, n, family, max_visual, max_seq=None, **kw):
     import time
     t0 = time.time()
     engines = []
     for i in range(n):
-        engines.append(E.DropoutEngine(cfg, family=family, max_seq=max_visual + 96, max_visual=max_visual, seed=50 + i, kv_format="fp16",
+        engines.append(E.DropoutEngine(cfg, family=family, max_seq=max_seq or max_visual + 96, max_visual=max_visual, seed=50 + i, kv_format="fp16",
                                        share_weights_with=engines[0] if engines else None, **kw))
     print(f"\n[{n} engines created in {time.time() - t0:.0f} s]", end="")
     return engines
@@ -321,5 +223,93 @@ def test_rider_step_instructblip_rule_llama7b_shapes_every_lane_vs_oracle(E, lla
     _group_vs_oracle(E, engines, refs, embs, spans, K8, steps, "llama-7b shapes, InstructBLIP rule, 16 lanes K = 8 (rider form)")
     worst = _solo_vs_oracle(engines[7], refs[7], embs[7], spans[7], K8, steps, 57, "never", "llama-7b shapes, InstructBLIP rule, lane 7 alone")
     print(f"  lane 7 alone: worst logits error {worst:.2e}")
+    for e in reversed(engines):
+        e.close()
+
+
+def _lane_record(e):
+    return [e.image_logits().copy(), e.logits().copy(), e.kv_sums().copy(), e.vision_uncert_dict()["epis_uncert_per_token"].copy(),
+            np.asarray(e.topk()[1]).copy()]
+
+
+@pytest.mark.parametrize("which,wfmt", [("llama_w", "bf16"), ("mistral_w", "bf16"), ("mistral_w", "fp8")])
+def test_batched_prefill_7b_widths_every_form_every_lane_vs_oracle(E, request, which, wfmt):
+    """(f) dd_lm_prefill_group at the 7B widths: nine prompts of 103 .. 250 positions laid back to back as ONE matrix of 9 x 256 = 2304 rows, which
+    every GEMM of the layers (K = 4096 / 11008 / 14336: 128 / 344 / 448 k-steps; EPI_QKV, EPI_RESID, EPI_SILU; bf16 and the fp8 scales) runs
+    through the large block — in each of its forms, tuning key 20 = 1 (LDS-DMA, 160 or 128 rows per launch), 0 (k_gemm_big), 8 and 10
+    (k_gemm_dma<.., 8 / 10> forced).  256 is no multiple of 160, so the 160-row blocks straddle sequences, and 2304 = 14 x 160 + 64 leaves a
+    partial last block; the spans start at different offsets and cross 64-key tiles.  After each prefill two group steps read the KV cache
+    that the batched QKV epilogue wrote per sequence.  The four forms and one prefill() per lane (under 1024 rows: k_gemm) must leave the same
+    bits — image logits, last-row logits, cache sums, uncertainties, top-k ids, both steps' logits, tokens — and the default form's run is
+    compared lane by lane with each lane's own oracle (fp8: the oracle on the dequantised weights)."""
+    import time
+    from dropoutdecoding_amd import _lib
+    from dropoutdecoding_amd.lm import dequantize_fp8, quantize_fp8
+    lib = _lib.load()
+    dims, w = request.getfixturevalue(which)
+    d = dims[1]
+    rc, cfg = RefCfg(*dims), E.LMConfig(*dims)
+    family, probs = (FAMILY_LLAVA, K4) if which == "llama_w" else (FAMILY_NEXT, K8)
+    T0s = [103, 250, 137, 199, 129, 241, 160, 117, 222]              # max 250 -> 256 rows per sequence; 137, 199, ... in (128, 256]
+    spans = [(2, 72), (30, 80), (60, 40), (5, 96), (50, 64), (100, 90), (0, 48), (20, 50), (120, 64)]   # (60, 40), (50, 64), (20, 50): across key 64
+    n, steps = len(T0s), 2
+    gen = torch.Generator().manual_seed(14)
+    embs = [torch.randn(T0, d, generator=gen) * 0.5 for T0 in T0s]
+    wo = w if wfmt != "fp8" else {k: (dequantize_fp8(*quantize_fp8(v)) if v.dim() == 2 and "embed_tokens" not in k else v) for k, v in w.items()}
+    refs = _oracle_lanes(family, rc, wo, probs, embs, spans, steps + 1)
+    del wo
+    engines = _lanes(E, cfg, n, family, 96, max_seq=320, weight_format=wfmt)
+    engines[0].load_state_dict(w)
+    xs = [x.cuda() for x in embs]
+    grp = E.EngineGroup(engines)
+    what = f"{which[:-2]}-7b shapes {wfmt}, batched prefill of {n} lanes ({n} x 256 rows)"
+    checks = [LaneCheck(f"{what}, lane {i}", e, r, probs) for i, (e, r) in enumerate(zip(engines, refs))]
+
+    def run(form):
+        """form: key 20's value, or None = one prefill() per lane"""
+        for i, e in enumerate(engines):
+            e.rng.manual_seed(50 + i)
+        if form is None:
+            for e, x, (s0, L) in zip(engines, xs, spans):
+                e.prefill(x, s0, L)
+        else:
+            lib.dd_set_tuning(20, form)
+            E.prefill_group(engines, xs, spans)
+        for e in engines:
+            e.set_eos([])
+        if form == 1:
+            for c in checks:
+                c.prefill()
+        rec = [_lane_record(e) for e in engines]
+        for s in range(steps):
+            grp.decode_step(probs)
+            for e, r in zip(engines, rec):
+                r += [e.base_logits().copy(), e.logits().copy(), e.last_step()["drop"].copy()]
+            if form == 1:
+                for c in checks:
+                    c.step(s)
+        for e, r in zip(engines, rec):
+            r.append(np.asarray(e.tokens()))
+        if form == 1:
+            for c in checks:
+                c.tokens()
+        return rec
+
+    t0 = time.time()
+    try:
+        outs = {form: run(form) for form in (1, 0, 8, 10)}
+    finally:
+        lib.dd_set_tuning(15, 1)
+        lib.dd_set_tuning(16, 1024)
+        lib.dd_set_tuning(20, 1)
+    outs["prefill() per lane"] = run(None)
+    print(f"\n[engine side: {n} lanes, 5 x (prefill + {steps} group steps) + comparisons in {time.time() - t0:.0f} s]", end="")
+    for form, recs in outs.items():
+        for i, (got, want) in enumerate(zip(recs, outs[1])):
+            for j, (a, b) in enumerate(zip(got, want)):
+                np.testing.assert_array_equal(a, b, err_msg=f"{what}: form {form} vs form 1, lane {i}, item {j} "
+                                                            "(0 image logits, 1 last logits, 2 kv sums, 3 epi, 4 top-k ids, then per step "
+                                                            "un-masked logits, logits, drop flags; last: tokens)")
+    _report(checks, what)
     for e in reversed(engines):
         e.close()

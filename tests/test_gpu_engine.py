@@ -952,11 +952,15 @@ def test_group_step_side_paths(E, kw, K):
 
 
 @pytest.mark.parametrize("dims,T0", [((512, 256, 512, 2, 2, 2), 1100),          # 16-tile matrices: part of one 32-tile column block
-                                     ((2048, 1024, 2816, 2, 8, 4), 1300)])      # several column blocks, K = 2816 (88 k-steps), GQA 2
+                                     ((2048, 1024, 2816, 2, 8, 4), 1300),       # several column blocks, K = 2816 (88 k-steps), GQA 2
+                                     ((512, 768, 1536, 2, 6, 3), 1103)])        # K = 768 / 1536: 24 / 48 k-steps, a multiple of the ring's 3 stages; GQA 2
 def test_prefill_gemm_block_shapes_and_orders_give_the_same_bits(E, dims, T0):
-    """The prefill GEMM has three forms — 128 x 128 blocks in row-major block order, the same in the XCD-aware order, and the
-    128 x 512 LDS-staged block used from 1024 rows on (k_gemm_big) — that issue the same MFMA sequence per accumulator tile:
-    image logits, last-row logits, the KV cache and the following ensemble steps must be bit-identical, and agree with the oracle."""
+    """The prefill GEMM has five forms: 128 x 128 blocks (k_gemm) in row-major block order and in the XCD-aware order, and from 1024 rows
+    on (tuning key 16) a large LDS-staged block in the form tuning key 20 selects — 0: k_gemm_big (128 x 512, register-staged), 8:
+    k_gemm_dma<.., 8> (128 x 512, LDS-DMA), 10: k_gemm_dma<.., 10> (160 x 512, LDS-DMA), 1 (default): one of the two k_gemm_dma blocks
+    per launch.  All issue the same MFMA sequence per accumulator tile: image logits, last-row logits, the KV cache and the following
+    ensemble steps must be bit-identical, and agree with the oracle.  The k-step counts cover every residue of the three-stage ring
+    (8 / 16 / 32 / 88 and 24 / 48 steps); no M is a multiple of 16."""
     from dropoutdecoding_amd import _lib
     lib = _lib.load()
     V, d, dff, nl, H, Hkv = dims
@@ -970,9 +974,11 @@ def test_prefill_gemm_block_shapes_and_orders_give_the_same_bits(E, dims, T0):
     e.load_state_dict(w)
     outs = []
     try:
-        for order, big in ((0, 0), (1, 0), (0, 1024), (1, 1024), (1, 128)):
+        for order, big, dma in ((0, 0, 1), (1, 0, 1), (0, 1024, 1), (1, 1024, 1), (1, 128, 1),
+                                (1, 1024, 0), (0, 1024, 0), (1, 1024, 8), (0, 1024, 8), (1, 1024, 10), (0, 1024, 10)):
             lib.dd_set_tuning(15, order)
             lib.dd_set_tuning(16, big)
+            lib.dd_set_tuning(20, dma)
             e.rng.manual_seed(3)
             e.prefill(x.cuda(), s0, L)
             rec = [e.image_logits().copy(), e.logits().copy(), e.kv_sums().copy()]
@@ -984,6 +990,7 @@ def test_prefill_gemm_block_shapes_and_orders_give_the_same_bits(E, dims, T0):
     finally:
         lib.dd_set_tuning(15, 1)
         lib.dd_set_tuning(16, 1024)
+        lib.dd_set_tuning(20, 1)
     for o in outs[1:]:
         for a, b in zip(o, outs[0]):
             np.testing.assert_array_equal(a, b)
