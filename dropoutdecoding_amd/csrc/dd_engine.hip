@@ -124,17 +124,17 @@ static int lm_create_impl(const dd_lm_config* c, dd_lm* parent, dd_lm** out) {
   const int d = h->d, dff = h->dff, T = h->T_cap;
   h->tp_world = c->reserved[0] > 1 ? c->reserved[0] : 1;
   h->tp_rank = h->tp_world > 1 ? c->reserved[1] : 0;
-  if (h->tp_world > 1 && (h->tp_rank < 0 || h->tp_rank >= h->tp_world || h->tp_world > 8 || c->weight_format == 1 || parent)) {
+  if (h->tp_world > 1 && (h->tp_rank < 0 || h->tp_rank >= h->tp_world || h->tp_world > 8 || c->weight_format == 1 || c->weight_format == 3 || parent)) {
     dd_set_error("dd_lm_create: tensor-parallel shard %d of %d (2..8 ranks, bf16 / fp16 weights, not a lane)", c->reserved[1], c->reserved[0]);
     delete h;
     return DD_EINVAL;
   }
-  h->fp8 = c->weight_format == 1 ? 1 : 0;
+  h->wq = c->weight_format == 1 ? DD_WQ_FP8 : (c->weight_format == 3 ? DD_WQ_MXFP4 : 0);
   h->wf = c->weight_format == 2 ? 1 : 0;
   h->kv16 = c->kv_format == 1 ? 1 : 0;
   DD_REQUIRE(c->kv_format == 0 || c->kv_format == 1, "dd_lm_create: unknown KV cache format %d", c->kv_format);
-  DD_REQUIRE(c->weight_format >= 0 && c->weight_format <= 2, "dd_lm_create: unknown weight format %d", c->weight_format);
-  const int wdiv = h->fp8 ? 2 : 1;   // u32x4 units per tile row: S*64 (bf16) or (S/2)*64 (fp8)
+  DD_REQUIRE(c->weight_format >= 0 && c->weight_format <= 3, "dd_lm_create: unknown weight format %d", c->weight_format);
+  const int wdiv = h->wq == DD_WQ_MXFP4 ? 4 : (h->wq ? 2 : 1);   // u32x4 units per tile row: S*64 (bf16), (S/2)*64 (fp8) or (S/4)*64 (MXFP4)
   if (parent) {
     // a lane: another sequence over the SAME weights (its own KV cache, state and scratch)
     const dd_lm_config& pc = parent->cfg;
@@ -157,18 +157,19 @@ static int lm_create_impl(const dd_lm_config* c, dd_lm* parent, dd_lm** out) {
     DA(w.wo, (size_t)(d / 16) * h->S_q * 64 / wdiv);
     DA(w.wgu, (size_t)(2 * dff / 16) * h->S_d * 64 / wdiv);
     DA(w.wdown, (size_t)(d / 16) * h->S_ff * 64 / wdiv);
-    if (h->fp8) {
-      DA(w.s_qkv, (size_t)h->qkv_tiles * 16);
-      DA(w.s_o, (size_t)d);
-      DA(w.s_gu, (size_t)2 * dff);
-      DA(w.s_down, (size_t)d);
+    if (h->wq) {       // fp8: one float per row; MXFP4: one u32 (four e8m0 bytes) per row and 128 k
+      const size_t md = h->wq == DD_WQ_MXFP4 ? h->S_d / 4 : 1, mq = h->wq == DD_WQ_MXFP4 ? h->S_q / 4 : 1, mf = h->wq == DD_WQ_MXFP4 ? h->S_ff / 4 : 1;
+      DA(w.s_qkv, (size_t)h->qkv_tiles * 16 * md);
+      DA(w.s_o, (size_t)d * mq);
+      DA(w.s_gu, (size_t)2 * dff * md);
+      DA(w.s_down, (size_t)d * mf);
     }
     DA(w.norm1, d);
     DA(w.norm2, d);
   }
   DA(h->lm_head, (size_t)(h->Vpad / 16) * h->S_d * 64 / wdiv);
-  if (h->fp8) {
-    DA(h->s_lm, (size_t)h->Vpad);
+  if (h->wq) {
+    DA(h->s_lm, (size_t)h->Vpad * (h->wq == DD_WQ_MXFP4 ? h->S_d / 4 : 1));
     size_t mx = (size_t)h->qkv_tiles * h->S_d;
     if ((size_t)(2 * dff / 16) * h->S_d > mx) mx = (size_t)(2 * dff / 16) * h->S_d;
     if ((size_t)(d / 16) * h->S_ff > mx) mx = (size_t)(d / 16) * h->S_ff;
@@ -316,8 +317,8 @@ extern "C" int dd_lm_load_tensor(dd_lm* h, int id, int layer, const uint16_t* sr
   }
   DD_REQUIRE((size_t)rows * cols == (size_t)er * ec && (er == 1 || (rows == er && cols == ec)),
              "dd_lm_load_tensor: tensor %d expects %d x %d, got %d x %d", id, er, ec, rows, cols);
-  DD_REQUIRE(!h->fp8 || id == DD_T_EMBED || id == DD_T_ATTN_NORM || id == DD_T_MLP_NORM || id == DD_T_FINAL_NORM,
-             "dd_lm_load_tensor: this engine stores fp8 weights; load matrices with dd_lm_load_tensor_fp8");
+  DD_REQUIRE(!h->wq || id == DD_T_EMBED || id == DD_T_ATTN_NORM || id == DD_T_MLP_NORM || id == DD_T_FINAL_NORM,
+             "dd_lm_load_tensor: this engine stores fp8 / MXFP4 weights; load matrices with dd_lm_load_tensor_fp8 / dd_lm_load_tensor_mxfp4");
   size_t n = (size_t)rows * cols;
   const uint16_t* dev = src;
   uint16_t* staging = nullptr;
@@ -358,7 +359,7 @@ extern "C" int dd_lm_load_tensor_fp8(dd_lm* h, int id, int layer, const uint8_t*
                                      int cols, int on_device) {
   DD_REQUIRE(h && q && row_scale, "dd_lm_load_tensor_fp8: null argument");
   DD_REQUIRE(!h->wsrc, "dd_lm_load_tensor_fp8: this handle borrows its weights (dd_lm_create_shared); load into the owner");
-  DD_REQUIRE(h->fp8, "dd_lm_load_tensor_fp8: the engine was created for bf16 weights (weight_format 0)");
+  DD_REQUIRE(h->wq == DD_WQ_FP8, "dd_lm_load_tensor_fp8: the engine was not created for fp8 weights (weight_format 1)");
   bool per_layer = id != DD_T_LM_HEAD;
   DD_REQUIRE(id == DD_T_LM_HEAD || (id >= DD_T_WQ && id <= DD_T_WDOWN && id != DD_T_MLP_NORM),
              "dd_lm_load_tensor_fp8: tensor id %d is not a matrix", id);
@@ -405,11 +406,97 @@ extern "C" int dd_lm_load_tensor_fp8(dd_lm* h, int id, int layer, const uint8_t*
   return DD_OK;
 }
 
+extern "C" int dd_lm_load_tensor_mxfp4(dd_lm* h, int id, int layer, const uint8_t* q, const uint8_t* scale, int rows, int cols,
+                                       int on_device) {
+  DD_REQUIRE(h && q && scale, "dd_lm_load_tensor_mxfp4: null argument");
+  DD_REQUIRE(!h->wsrc, "dd_lm_load_tensor_mxfp4: this handle borrows its weights (dd_lm_create_shared); load into the owner");
+  DD_REQUIRE(h->wq == DD_WQ_MXFP4, "dd_lm_load_tensor_mxfp4: the engine was not created for MXFP4 weights (weight_format 3)");
+  bool per_layer = id != DD_T_LM_HEAD;
+  DD_REQUIRE(id == DD_T_LM_HEAD || (id >= DD_T_WQ && id <= DD_T_WDOWN && id != DD_T_MLP_NORM),
+             "dd_lm_load_tensor_mxfp4: tensor id %d is not a matrix", id);
+  DD_REQUIRE(!per_layer || (layer >= 0 && layer < h->Lyr), "dd_lm_load_tensor_mxfp4: layer %d out of range", layer);
+  const int d = h->d, dff = h->dff;
+  int er = 0, ec = 0;
+  switch (id) {
+    case DD_T_LM_HEAD: er = h->V, ec = d; break;
+    case DD_T_WQ: er = h->q_dim, ec = d; break;
+    case DD_T_WK: case DD_T_WV: er = h->kv_dim, ec = d; break;
+    case DD_T_WO: er = d, ec = h->q_dim; break;
+    case DD_T_WGATE: case DD_T_WUP: er = dff, ec = d; break;
+    case DD_T_WDOWN: er = d, ec = dff; break;
+  }
+  DD_REQUIRE(rows == er && cols == ec, "dd_lm_load_tensor_mxfp4: tensor %d expects %d x %d, got %d x %d", id, er, ec, rows, cols);
+  const size_t nq = (size_t)rows * (cols / 2), ns = (size_t)rows * (cols / 32);
+  // staging: [elements | scales | flag] in one allocation (the flag: a scale byte outside [7, 247] met while packing)
+  const size_t off_s = on_device ? 0 : (nq + 15) / 16 * 16, off_f = on_device ? 0 : off_s + (ns + 15) / 16 * 16;
+  uint8_t* stg = nullptr;
+  DD_HIP(hipMalloc((void**)&stg, off_f + 16));
+  hipError_t e = hipMemset(stg + off_f, 0, 16);
+  const uint8_t *dq = q, *ds = scale;
+  if (!on_device) {
+    if (e == hipSuccess) e = hipMemcpy(stg, q, nq, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(stg + off_s, scale, ns, hipMemcpyHostToDevice);
+    dq = stg, ds = stg + off_s;
+  }
+  if (e != hipSuccess) {
+    (void)hipFree(stg);
+    dd_set_error("dd_lm_load_tensor_mxfp4: staging copy failed: %s", hipGetErrorString(e));
+    return DD_EHIP;
+  }
+  int32_t* bad = (int32_t*)(stg + off_f);
+  LayerW* w = per_layer ? &h->lw[layer] : nullptr;
+  auto sw = [](float* p) { return (uint32_t*)p; };
+  int rc = DD_OK;
+  switch (id) {
+    case DD_T_WQ: rc = ddk_pack_weight_mxfp4(dq, ds, rows, cols, w->wqkv, sw(w->s_qkv), 0, 1, PACK_ROPE, h->q_tiles, bad, nullptr); break;
+    case DD_T_WK: rc = ddk_pack_weight_mxfp4(dq, ds, rows, cols, w->wqkv, sw(w->s_qkv), h->q_tiles, 1, PACK_ROPE, h->k_tiles, bad, nullptr); break;
+    case DD_T_WV: rc = ddk_pack_weight_mxfp4(dq, ds, rows, cols, w->wqkv, sw(w->s_qkv), h->q_tiles + h->k_tiles, 1, PACK_PLAIN, h->k_tiles, bad, nullptr); break;
+    case DD_T_WO: rc = ddk_pack_weight_mxfp4(dq, ds, rows, cols, w->wo, sw(w->s_o), 0, 1, PACK_PLAIN, d / 16, bad, nullptr); break;
+    case DD_T_WGATE: rc = ddk_pack_weight_mxfp4(dq, ds, rows, cols, w->wgu, sw(w->s_gu), 0, 2, PACK_PLAIN, dff / 16, bad, nullptr); break;
+    case DD_T_WUP: rc = ddk_pack_weight_mxfp4(dq, ds, rows, cols, w->wgu, sw(w->s_gu), 1, 2, PACK_PLAIN, dff / 16, bad, nullptr); break;
+    case DD_T_WDOWN: rc = ddk_pack_weight_mxfp4(dq, ds, rows, cols, w->wdown, sw(w->s_down), 0, 1, PACK_PLAIN, d / 16, bad, nullptr); break;
+    case DD_T_LM_HEAD: rc = ddk_pack_weight_mxfp4(dq, ds, rows, cols, h->lm_head, sw(h->s_lm), 0, 1, PACK_PLAIN, h->Vpad / 16, bad, nullptr); break;
+  }
+  int32_t bad_host = 0;
+  e = hipDeviceSynchronize();
+  if (e == hipSuccess && rc == DD_OK) e = hipMemcpy(&bad_host, bad, 4, hipMemcpyDeviceToHost);
+  (void)hipFree(stg);
+  if (rc != DD_OK) return rc;
+  DD_HIP(e);
+  DD_REQUIRE(!bad_host, "dd_lm_load_tensor_mxfp4: tensor %d holds a scale byte outside [7, 247] (block exponents -120..120)", id);
+  return DD_OK;
+}
+
 extern "C" int dd_lm_load_synthetic(dd_lm* h, uint32_t seed, float std) {
   DD_REQUIRE(h && !h->wsrc, "dd_lm_load_synthetic: null handle, or a handle that borrows its weights");
   DD_REQUIRE(h, "dd_lm_load_synthetic: null handle");
   const int d = h->d, dff = h->dff;
-  if (h->fp8) {   // random finite e4m3 bytes (|q| <= 240, rms ~ 40) with a constant row scale that gives ~std
+  if (h->wq == DD_WQ_MXFP4) {   // random e2m1 codes (rms 2.93) with one constant block scale: the power of two nearest std / 2.93
+    uint32_t s4 = seed * 2654435761u + 13;
+    int e = (int)lrintf(log2f((std > 0.f ? std : 1e-30f) / 2.926f));
+    e = e < -120 ? -120 : (e > 120 ? 120 : e);
+    const uint32_t sb = (uint32_t)(e + 127) * 0x01010101u;
+    for (int l = 0; l < h->Lyr; ++l) {
+      LayerW& w = h->lw[l];
+      RC(ddk_fill_synthetic_mxfp4((uint8_t*)w.wqkv, (size_t)h->qkv_tiles * h->S_d * 256, s4++, nullptr));
+      RC(ddk_fill_synthetic_mxfp4((uint8_t*)w.wo, (size_t)(d / 16) * h->S_q * 256, s4++, nullptr));
+      RC(ddk_fill_synthetic_mxfp4((uint8_t*)w.wgu, (size_t)(2 * dff / 16) * h->S_d * 256, s4++, nullptr));
+      RC(ddk_fill_synthetic_mxfp4((uint8_t*)w.wdown, (size_t)(d / 16) * h->S_ff * 256, s4++, nullptr));
+      RC(ddk_fill_const_u32((uint32_t*)w.s_qkv, (size_t)h->qkv_tiles * 4 * h->S_d, sb, nullptr));
+      RC(ddk_fill_const_u32((uint32_t*)w.s_o, (size_t)(d / 16) * 4 * h->S_q, sb, nullptr));
+      RC(ddk_fill_const_u32((uint32_t*)w.s_gu, (size_t)(2 * dff / 16) * 4 * h->S_d, sb, nullptr));
+      RC(ddk_fill_const_u32((uint32_t*)w.s_down, (size_t)(d / 16) * 4 * h->S_ff, sb, nullptr));
+      RC(ddk_fill_const_f32(w.norm1, d, 1.0f, nullptr));
+      RC(ddk_fill_const_f32(w.norm2, d, 1.0f, nullptr));
+    }
+    RC(ddk_fill_synthetic_mxfp4((uint8_t*)h->lm_head, (size_t)(h->Vpad / 16) * h->S_d * 256, s4++, nullptr));
+    RC(ddk_fill_const_u32((uint32_t*)h->s_lm, (size_t)(h->Vpad / 16) * 4 * h->S_d, sb, nullptr));
+    RC(ddk_fill_const_f32(h->final_norm, d, 1.0f, nullptr));
+    RC(ddk_fill_synthetic(h->embed, (size_t)h->V * d, s4++, 1.0f, nullptr));
+    DD_HIP(hipDeviceSynchronize());
+    return DD_OK;
+  }
+  if (h->wq) {   // random finite e4m3 bytes (|q| <= 240, rms ~ 40) with a constant row scale that gives ~std
     uint32_t s8 = seed * 2654435761u + 7;
     const float sc = std / 40.0f;
     for (int l = 0; l < h->Lyr; ++l) {
@@ -629,13 +716,14 @@ static int prefill_layers(dd_lm* h, int T0, const uint8_t* drop_plane, int drop_
   const int d = h->d, dff = h->dff;
   // fp8 storage: the prefill GEMM runs on a bf16 expansion of ONE matrix at a time (exact), scales in its epilogue
   auto wsel = [&](GemmArgs& g, u32x4_t* W, float* scale, int n_tiles, int S) -> int {
-    if (!h->fp8) {
+    if (!h->wq) {
       g.W = W;
       return DD_OK;
     }
-    int rc = ddk_dequant_tiles(W, h->deq_tmp, n_tiles, S, st);
-    g.W = h->deq_tmp, g.wscale = scale;
-    return rc;
+    g.W = h->deq_tmp;
+    if (h->wq == DD_WQ_MXFP4) return ddk_dequant_tiles_mxfp4(W, (const uint32_t*)scale, h->deq_tmp, n_tiles, S, st);   // block scales applied: no wscale
+    g.wscale = scale;
+    return ddk_dequant_tiles(W, h->deq_tmp, n_tiles, S, st);
   };
   for (int l = 0; l < h->Lyr; ++l) {
     LayerW& w = h->lw[l];
@@ -687,8 +775,11 @@ static int prefill_head(dd_lm* h, const int32_t* row_index, int n_rows, float* l
   memset(&g, 0, sizeof(g));
   g.wf = h->wf;
   g.a_hi = h->p1_hi, g.a_lo = h->p1_lo, g.M = n_rows, g.S = h->S_d, g.n_tiles = h->Vpad / 16;
-  if (!h->fp8) {
+  if (!h->wq) {
     g.W = h->lm_head;
+  } else if (h->wq == DD_WQ_MXFP4) {
+    RC(ddk_dequant_tiles_mxfp4(h->lm_head, (const uint32_t*)h->s_lm, h->deq_tmp, h->Vpad / 16, h->S_d, st));
+    g.W = h->deq_tmp;
   } else {
     RC(ddk_dequant_tiles(h->lm_head, h->deq_tmp, h->Vpad / 16, h->S_d, st));
     g.W = h->deq_tmp, g.wscale = h->s_lm;
@@ -833,13 +924,14 @@ extern "C" int dd_lm_prefill_group(dd_lm* const* lanes, int n, const float* cons
   for (int i = 0; i < n; ++i)
     DD_HIP(hipMemcpyAsync(bx + (size_t)i * seq_rows * d, embeds[i], (size_t)T0s[i] * d * 4, hipMemcpyDeviceToDevice, st));
   auto wsel = [&](GemmArgs& g, u32x4_t* W, float* scale, int n_tiles, int S) -> int {      // as in prefill_layers
-    if (!h0->fp8) {
+    if (!h0->wq) {
       g.W = W;
       return DD_OK;
     }
-    int rc = ddk_dequant_tiles(W, h0->deq_tmp, n_tiles, S, st);
-    g.W = h0->deq_tmp, g.wscale = scale;
-    return rc;
+    g.W = h0->deq_tmp;
+    if (h0->wq == DD_WQ_MXFP4) return ddk_dequant_tiles_mxfp4(W, (const uint32_t*)scale, h0->deq_tmp, n_tiles, S, st);
+    g.wscale = scale;
+    return ddk_dequant_tiles(W, h0->deq_tmp, n_tiles, S, st);
   };
   for (int l = 0; l < h0->Lyr; ++l) {
     LayerW& w = h0->lw[l];
@@ -934,7 +1026,7 @@ static int prefill_extend_rows(dd_lm* h, const float* embeds, int n, hipStream_t
     GemvArgs a;
     memset(&a, 0, sizeof(a));
     a.wf = h->wf;
-    a.W = w.wqkv, a.S = h->S_d, a.n_tiles = h->qkv_tiles, a.xop = h->xop_d, a.fp8 = h->fp8, a.wscale = w.s_qkv;
+    a.W = w.wqkv, a.S = h->S_d, a.n_tiles = h->qkv_tiles, a.xop = h->xop_d, a.wq = h->wq, a.wscale = w.s_qkv;
     a.ssq_in = h->ssq_a, a.ssq_n = ssq_n, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps;
     a.qbuf = h->qbuf, a.knew = h->chunk_k, a.vnew = h->chunk_v, a.q_tiles = h->q_tiles, a.k_tiles = h->k_tiles;
     a.q_dim = h->q_dim, a.kv_dim = h->kv_dim, a.rope_cos = h->rope_cos, a.rope_sin = h->rope_sin, a.state = h->chunk_states;
@@ -961,18 +1053,18 @@ static int prefill_extend_rows(dd_lm* h, const float* embeds, int n, hipStream_t
     }
     memset(&a, 0, sizeof(a));
     a.wf = h->wf;
-    a.W = w.wo, a.S = h->S_q, a.n_tiles = d / 16, a.xop = h->xop_q, a.fp8 = h->fp8, a.wscale = w.s_o;
+    a.W = w.wo, a.S = h->S_q, a.n_tiles = d / 16, a.xop = h->xop_q, a.wq = h->wq, a.wscale = w.s_o;
     a.out = h->xa, a.ldo = d, a.normw_next = w.norm2, a.xop_next = h->xop_d, a.S_next = h->S_d, a.ssq_out = h->ssq_b, a.ssq_ld = d / 16;
     RC(gemv(EPI_RESID, a));
     memset(&a, 0, sizeof(a));
     a.wf = h->wf;
-    a.W = w.wgu, a.S = h->S_d, a.n_tiles = dff / 16, a.xop = h->xop_d, a.fp8 = h->fp8, a.wscale = w.s_gu;
+    a.W = w.wgu, a.S = h->S_d, a.n_tiles = dff / 16, a.xop = h->xop_d, a.wq = h->wq, a.wscale = w.s_gu;
     a.ssq_in = h->ssq_b, a.ssq_n = d / 16, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps;
     a.xop_next = h->xop_ff, a.S_next = h->S_ff;
     RC(gemv(EPI_SILU, a));
     memset(&a, 0, sizeof(a));
     a.wf = h->wf;
-    a.W = w.wdown, a.S = h->S_ff, a.n_tiles = d / 16, a.xop = h->xop_ff, a.fp8 = h->fp8, a.wscale = w.s_down;
+    a.W = w.wdown, a.S = h->S_ff, a.n_tiles = d / 16, a.xop = h->xop_ff, a.wq = h->wq, a.wscale = w.s_down;
     a.out = h->xa, a.ldo = d, a.normw_next = (l + 1 < h->Lyr) ? h->lw[l + 1].norm1 : h->final_norm;
     a.xop_next = h->xop_d, a.S_next = h->S_d, a.ssq_out = h->ssq_a, a.ssq_ld = d / 16;
     RC(gemv(EPI_RESID, a));
@@ -1126,7 +1218,7 @@ int lm_sweep(dd_lm* h, int nb, const uint8_t* bits, int row0, float* logits_out,
     memset(&a, 0, sizeof(a));
     a.wf = h->wf;
     a.W = w.wqkv, a.S = h->S_d, a.n_tiles = h->qkv_tiles, a.nb = nb, a.xop = h->xop_d;
-    a.fp8 = h->fp8, a.wscale = w.s_qkv;
+    a.wq = h->wq, a.wscale = w.s_qkv;
     a.ssq_in = h->ssq_a, a.ssq_n = ssq_n, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps;
     a.qbuf = h->qbuf, a.knew = knew, a.vnew = vnew, a.q_tiles = h->q_tiles, a.k_tiles = h->k_tiles;
     a.q_dim = h->q_dim, a.kv_dim = h->kv_dim, a.rope_cos = h->rope_cos, a.rope_sin = h->rope_sin, a.state = h->state;
@@ -1164,19 +1256,19 @@ int lm_sweep(dd_lm* h, int nb, const uint8_t* bits, int row0, float* logits_out,
     memset(&a, 0, sizeof(a));
     a.wf = h->wf;
     a.W = w.wo, a.S = h->S_q, a.n_tiles = d / 16, a.nb = nb, a.xop = h->xop_q;
-    a.fp8 = h->fp8, a.wscale = w.s_o;
+    a.wq = h->wq, a.wscale = w.s_o;
     a.out = h->xa, a.ldo = d, a.normw_next = w.norm2, a.xop_next = h->xop_d, a.S_next = h->S_d, a.ssq_out = h->ssq_b, a.ssq_ld = d / 16;
     RC(gemv(EPI_RESID, a));
     memset(&a, 0, sizeof(a));
     a.wf = h->wf;
     a.W = w.wgu, a.S = h->S_d, a.n_tiles = dff / 16, a.nb = nb, a.xop = h->xop_d;
-    a.fp8 = h->fp8, a.wscale = w.s_gu;
+    a.wq = h->wq, a.wscale = w.s_gu;
     a.ssq_in = h->ssq_b, a.ssq_n = d / 16, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps, a.xop_next = h->xop_ff, a.S_next = h->S_ff;
     RC(gemv(EPI_SILU, a));
     memset(&a, 0, sizeof(a));
     a.wf = h->wf;
     a.W = w.wdown, a.S = h->S_ff, a.n_tiles = d / 16, a.nb = nb, a.xop = h->xop_ff;
-    a.fp8 = h->fp8, a.wscale = w.s_down;
+    a.wq = h->wq, a.wscale = w.s_down;
     a.out = h->xa, a.ldo = d, a.normw_next = (l + 1 < h->Lyr) ? h->lw[l + 1].norm1 : h->final_norm;
     a.xop_next = h->xop_d, a.S_next = h->S_d, a.ssq_out = h->ssq_a, a.ssq_ld = d / 16;
     RC(gemv(EPI_RESID, a));
@@ -1186,7 +1278,7 @@ int lm_sweep(dd_lm* h, int nb, const uint8_t* bits, int row0, float* logits_out,
   memset(&a, 0, sizeof(a));
   a.wf = h->wf;
   a.W = h->lm_head, a.S = h->S_d, a.n_tiles = h->Vpad / 16, a.nb = nb, a.xop = h->xop_d;
-  a.fp8 = h->fp8, a.wscale = h->s_lm;
+  a.wq = h->wq, a.wscale = h->s_lm;
   a.ssq_in = h->ssq_a, a.ssq_n = ssq_n, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps;
   a.out = logits_out, a.ldo = h->Vpad, a.n_valid = h->V;
   if (!lanes) a.state = h->state;      // a finished sequence keeps the logits of its EOS step (the group's fused base rows go
@@ -1441,7 +1533,7 @@ static int lm_sweep_groups(dd_lm* h, dd_lm* const* qs, int ng, int K, hipStream_
     memset(&a, 0, sizeof(a));
     a.wf = h->wf;
     a.W = w.wqkv, a.S = h->S_d, a.n_tiles = h->qkv_tiles, a.nb = K, a.xop = h->xop_d, a.n_groups = planes, a.nb_rider = n_rider, a.half_planes = hp;
-    a.fp8 = h->fp8, a.wscale = w.s_qkv;
+    a.wq = h->wq, a.wscale = w.s_qkv;
     a.ssq_in = h->ssq_a, a.ssq_n = ssq_n, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps;
     a.qbuf = h->qbuf, a.q_tiles = h->q_tiles, a.k_tiles = h->k_tiles;
     a.q_dim = h->q_dim, a.kv_dim = h->kv_dim, a.rope_cos = h->rope_cos, a.rope_sin = h->rope_sin, a.state = qs[0]->state;
@@ -1539,7 +1631,7 @@ static int lm_sweep_groups(dd_lm* h, dd_lm* const* qs, int ng, int K, hipStream_
     memset(&a, 0, sizeof(a));
     a.wf = h->wf;
     a.W = w.wo, a.S = h->S_q, a.n_tiles = d / 16, a.nb = K, a.xop = h->xop_q, a.n_groups = planes, a.nb_rider = n_rider, a.half_planes = hp;
-    a.fp8 = h->fp8, a.wscale = w.s_o;
+    a.wq = h->wq, a.wscale = w.s_o;
     a.out = h->xa, a.ldo = d, a.normw_next = w.norm2, a.xop_next = h->xop_d, a.S_next = h->S_d, a.ssq_out = h->ssq_b, a.ssq_ld = d / 16;
     a.part = h->gemv_part, a.part_floats = h->gemv_part_floats;
     RC(on_family(h, st, 2, [&](hipStream_t s2) { return ddk_gemv_groups(EPI_RESID, a, s2); }));
@@ -1547,7 +1639,7 @@ static int lm_sweep_groups(dd_lm* h, dd_lm* const* qs, int ng, int K, hipStream_
     memset(&a, 0, sizeof(a));
     a.wf = h->wf;
     a.W = w.wgu, a.S = h->S_d, a.n_tiles = dff / 16, a.nb = K, a.xop = h->xop_d, a.n_groups = planes, a.nb_rider = n_rider, a.half_planes = hp;
-    a.fp8 = h->fp8, a.wscale = w.s_gu;
+    a.wq = h->wq, a.wscale = w.s_gu;
     a.ssq_in = h->ssq_b, a.ssq_n = d / 16, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps;
     a.xop_next = h->xop_ff, a.S_next = h->S_ff;
     a.part = h->gemv_part, a.part_floats = h->gemv_part_floats;
@@ -1556,7 +1648,7 @@ static int lm_sweep_groups(dd_lm* h, dd_lm* const* qs, int ng, int K, hipStream_
     memset(&a, 0, sizeof(a));
     a.wf = h->wf;
     a.W = w.wdown, a.S = h->S_ff, a.n_tiles = d / 16, a.nb = K, a.xop = h->xop_ff, a.n_groups = planes, a.nb_rider = n_rider, a.half_planes = hp;
-    a.fp8 = h->fp8, a.wscale = w.s_down;
+    a.wq = h->wq, a.wscale = w.s_down;
     a.out = h->xa, a.ldo = d, a.normw_next = (l + 1 < h->Lyr) ? h->lw[l + 1].norm1 : h->final_norm;
     a.xop_next = h->xop_d, a.S_next = h->S_d, a.ssq_out = h->ssq_a, a.ssq_ld = d / 16;
     a.part = h->gemv_part, a.part_floats = h->gemv_part_floats;
@@ -1569,7 +1661,7 @@ static int lm_sweep_groups(dd_lm* h, dd_lm* const* qs, int ng, int K, hipStream_
   memset(&a, 0, sizeof(a));
   a.wf = h->wf;
   a.W = h->lm_head, a.S = h->S_d, a.n_tiles = h->Vpad / 16, a.nb = K, a.xop = h->xop_d, a.n_groups = planes, a.nb_rider = n_rider, a.half_planes = hp;
-  a.fp8 = h->fp8, a.wscale = h->s_lm;
+  a.wq = h->wq, a.wscale = h->s_lm;
   a.ssq_in = h->ssq_a, a.ssq_n = ssq_n, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps;
   for (int g = 0; g < ng; ++g) {
     a.out_g[g] = qs[g]->member_logits;
@@ -1688,7 +1780,7 @@ void dd_engine_set_half_planes(int on) { g_half_planes = on; }
 static bool half_planes_ok(dd_lm* const* lanes, int n, int K) {
   if (!g_half_planes || K < 1 || K > 4 || g_pair_sweeps < 8 || n < 16) return false;
   dd_lm* h0 = lanes[0];
-  if (!h0->kv16 || h0->fp8 || !h0->gemv_part) return false;
+  if (!h0->kv16 || h0->wq || !h0->gemv_part) return false;
   const int qt = h0->qkv_tiles, gt = 2 * h0->dff / 16;
   if (h0->S_d != 128 || h0->S_q != 128 || !(h0->S_ff == 8 * 43 || h0->S_ff == 8 * 56) || qt < 64 || gt < 64 || h0->d / 16 < 64 || h0->Vpad / 16 < 64)
     return false;
@@ -1714,7 +1806,8 @@ static int rider_branches(dd_lm* const* lanes, int n, int K, int* gs_out = nullp
   if (!h0->kv16 || !h0->gemv_part) return 0;
   // shapes with nine-plane kernels (dd_gemv.hip try_slices9 / try_slices9_fp8)
   const int qt = h0->qkv_tiles, gt = 2 * h0->dff / 16;
-  if (h0->fp8) {                 // fp8 tiles: K = 4096 for qkv / o / gate-up / lm_head, K = 14336 for down (Mistral-7B: BASELINE config 5)
+  if (h0->wq == DD_WQ_MXFP4) return 0;   // MXFP4 tiles have no nine-plane kernels: the classic form
+  if (h0->wq) {                 // fp8 tiles: K = 4096 for qkv / o / gate-up / lm_head, K = 14336 for down (Mistral-7B: BASELINE config 5)
     if (h0->S_d != 128 || h0->S_q != 128 || h0->S_ff != 8 * 56 || qt < 64 || gt < 64 || h0->d / 16 < 64 || h0->Vpad / 16 < 64) return 0;
   } else if (h0->S_d != 128 || h0->S_q != 128 || !(h0->S_ff == 8 * 43 || h0->S_ff == 8 * 56) || (qt % 16) != 0 || qt / 16 * 4 > 256 ||
              gt < 64 || h0->d / 16 < 64 || h0->Vpad / 16 < 64) {
@@ -2064,7 +2157,7 @@ static int lm_sweep_spec(dd_lm* h, int K, hipStream_t st) {
   RC(ddk_embed_rows_lanes(h->embed, d, el, 16, h->xa, h->lw[0].norm1, h->xop_d, h->ssq_a, d / 16, st, h->wf));
   int ssq_n = 1;
   auto common = [&](GemvArgs& a) {
-    a.nb = K, a.n_groups = 2, a.fp8 = h->fp8, a.state = h->state, a.wf = h->wf;
+    a.nb = K, a.n_groups = 2, a.wq = h->wq, a.state = h->state, a.wf = h->wf;
     a.part = h->gemv_part, a.part_floats = h->gemv_part_floats;
   };
   for (int l = 0; l < h->Lyr; ++l) {
@@ -2701,7 +2794,7 @@ extern "C" double dd_lm_step_algorithmic_bytes(const dd_lm* h, int K) {
   // members), 1 for the stock greedy step.  W_lm in bf16; kv_tok at the cache's storage width (fp32 here).
   double params = (double)h->Lyr * ((double)(h->q_dim + 2 * h->kv_dim) * h->d + (double)h->d * h->q_dim + 3.0 * h->d * h->dff) +
                   (double)h->V * h->d;
-  double w = params * (h->fp8 ? 1.0 : 2.0);
+  double w = params * (h->wq == DD_WQ_MXFP4 ? 0.5 + 1.0 / 32.0 : (h->wq ? 1.0 : 2.0));
   double kv_tok = (double)h->Lyr * 2 * h->kv_dim * (h->kv16 ? 2.0 : 4.0);
   int sweeps = K > 0 ? 1 + (K + 7) / 8 : 1;
   return sweeps * (w + (double)h->T_host * kv_tok);

@@ -14,7 +14,7 @@
 struct LayerW {
   u32x4_t *wqkv, *wo, *wgu, *wdown;
   float *norm1, *norm2;
-  float *s_qkv = nullptr, *s_o = nullptr, *s_gu = nullptr, *s_down = nullptr;   // fp8: per-row scales, packed order
+  float *s_qkv = nullptr, *s_o = nullptr, *s_gu = nullptr, *s_down = nullptr;   // fp8: per-row scales, packed order; MXFP4: u32 block-scale words
 };
 
 struct dd_lm {
@@ -40,10 +40,10 @@ struct dd_lm {
   std::vector<LayerW> lw;
   u32x4_t* lm_head = nullptr;
   float* s_lm = nullptr;
-  int fp8 = 0;                 // weight storage: 0 bf16, 1 OCP e4m3fn + per-row scales
+  int wq = 0;                  // weight storage: 0 16-bit, 1 OCP e4m3fn + per-row scales (DD_WQ_FP8), 2 OCP MXFP4 (DD_WQ_MXFP4)
   int wf = 0;                  // 16-bit weight / operand type: 0 bf16, 1 fp16 (weight_format 2: fp16 checkpoints stay exact)
   int kv16 = 0;                // KV cache storage: 0 fp32, 1 fp16 (the reference's cache width; layouts in dd_lm_kernels.h)
-  u32x4_t* deq_tmp = nullptr;  // fp8: bf16 tiles of ONE matrix for the prefill GEMM
+  u32x4_t* deq_tmp = nullptr;  // fp8 / MXFP4: bf16 tiles of ONE matrix for the prefill GEMM
   float* final_norm = nullptr;
   uint16_t* embed = nullptr;
   float *rope_cos = nullptr, *rope_sin = nullptr;

@@ -20,7 +20,7 @@
 //       8 consecutive KiB) instead of one contiguous chunk per wave
 // Everything behind the LDS reduction of an 8-row pass, for the TILES tiles tile0.. of tile group tg (k_gemv: tg = blockIdx.x; k_gemv_loop walks
 // several groups per workgroup).  red: [TILES][8 waves][256] accumulators as the waves stored them; rstd_sh must be visible (barrier before the call).
-template <int EPI, int TILES, int FP8, int WF>
+template <int EPI, int TILES, int WQ, int WF>
 __device__ __forceinline__ void gemv8_epilogue(const GemvArgs& a, const int tile0, const int tg, const float* red, const float* rstd_sh, float* ssq_sh,
                                                const float pre0, const float pre1) {
   // D[n][c]: lane = (n>>2)*16 + c, reg = n&3.  y[m][n] = sum_w (D_w[n][m] + D_w[n][m+8])   (hi + lo columns)
@@ -35,7 +35,7 @@ __device__ __forceinline__ void gemv8_epilogue(const GemvArgs& a, const int tile
       const float* r = &red[(tt * GEMV_WAVES + w) * 256];
       y += (r[o] + r[o + 32]) + (r[256 + o] + r[256 + o + 32]);
     }
-    if (FP8) y *= a.wscale[(size_t)(tile0 + tt) * 16 + n];
+    if (WQ == DD_WQ_FP8) y *= a.wscale[(size_t)(tile0 + tt) * 16 + n];   // (MXFP4: the block scales went in with the expansion)
     return y;
   };
 
@@ -107,7 +107,7 @@ __device__ __forceinline__ void gemv8_epilogue(const GemvArgs& a, const int tile
   }
 }
 
-template <int EPI, int TILES, int U, int NT, int ILV, int FP8 = 0, int PIPE = 0, int WF = 0>
+template <int EPI, int TILES, int U, int NT, int ILV, int WQ = 0, int PIPE = 0, int WF = 0>
 __global__ __launch_bounds__(GEMV_THREADS) void k_gemv(GemvArgs a) {
   __shared__ float red[TILES * GEMV_WAVES * 256];
   __shared__ float rstd_sh[8];
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void k_gemv(GemvArgs a) {
     }
   };
 
-  if constexpr (FP8) {
+  if constexpr (WQ == DD_WQ_FP8) {
     // fp8 weights: one 1 KiB load = 64 k of a tile row = two MFMA k-steps; wave w takes 64-k steps w, w+8, ...
     // (uneven tails allowed: K = 11008 has 172 such steps)
     const int S2 = S >> 1;
@@ -205,6 +205,52 @@ __global__ __launch_bounds__(GEMV_THREADS) void k_gemv(GemvArgs a) {
       }
     }
   }
+  if constexpr (WQ == DD_WQ_MXFP4) {
+    // MXFP4 weights: one 1 KiB load = 128 k of a tile row = FOUR MFMA k-steps (4 s4 .. 4 s4 + 3, in order) after the exact expansion;
+    // wave w takes 128-k loads w, w+8, ... (uneven tails allowed: K = 11008 has 86 loads, K = 256 gives work to two waves only)
+    const int S4 = S >> 2;
+    const u32x4_t* wq[TILES];
+    const uint32_t* sq[TILES];
+#pragma unroll
+    for (int t = 0; t < TILES; ++t) {
+      wq[t] = a.W + (size_t)(tile0 + t) * S4 * 64 + lane;
+      sq[t] = (const uint32_t*)a.wscale + (size_t)(tile0 + t) * S4 * 16 + (lane & 15);
+    }
+    const u32x4_t* xq = a.xop + lane;
+    constexpr int UF = 4;   // loads in flight per tile = 16 bf16 k-steps
+    for (int s4 = wave; s4 < S4; s4 += GEMV_WAVES * UF) {
+      u32x4_t wf[TILES][UF], b[UF][4];
+      uint32_t sc[TILES][UF];
+#pragma unroll
+      for (int u = 0; u < UF; ++u) {
+        int ss = s4 + u * GEMV_WAVES;
+        if (ss < S4) {
+#pragma unroll
+          for (int t = 0; t < TILES; ++t) {
+            wf[t][u] = ldw(wq[t] + (size_t)ss * 64);
+            sc[t][u] = sq[t][(size_t)ss * 16];
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) b[u][j] = xq[(size_t)(4 * ss + j) * 64];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < UF; ++u) {
+        int ss = s4 + u * GEMV_WAVES;
+        if (ss < S4) {
+#pragma unroll
+          for (int t = 0; t < TILES; ++t) {
+            u32x4_t k[4];
+            mxfp4x32_to_bf16(wf[t][u], sc[t][u], k);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, k[j]),
+                                                               __builtin_bit_cast(bf16x8_t, b[u][j]), acc[t], 0, 0, 0);
+          }
+        }
+      }
+    }
+  }
   auto finish_rstd = [&]() {
     if (has_ssq) {
       const int i0 = 4 * lane;
@@ -218,7 +264,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void k_gemv(GemvArgs a) {
       if (lane == 0) rstd_sh[wave] = 1.0f / sqrtf(v * a.inv_k + a.eps);
     }
   };
-  if constexpr (!FP8 && PIPE == 0) {
+  if constexpr (!WQ && PIPE == 0) {
     // batches: U steps requested together, then consumed; the other resident waves cover the drain
     int s = 0;
     for (; s + U <= spw; s += U) {
@@ -256,7 +302,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void k_gemv(GemvArgs a) {
       }
     }
   }
-  if constexpr (!FP8 && PIPE == 1) {
+  if constexpr (!WQ && PIPE == 1) {
     // Ring of U requests per wave: slot u is consumed by its MFMA and immediately re-requested U steps ahead, so the
     // wave always has ~U weight tiles in flight (no drain between batches).
     const int n = spw;
@@ -299,7 +345,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void k_gemv(GemvArgs a) {
   for (int t = 0; t < TILES; ++t) *(f32x4_t*)&red[(t * GEMV_WAVES + wave) * 256 + lane * 4] = acc[t];
   __syncthreads();
 
-  gemv8_epilogue<EPI, TILES, FP8, WF>(a, tile0, blockIdx.x, red, rstd_sh, ssq_sh, pre0, pre1);
+  gemv8_epilogue<EPI, TILES, WQ, WF>(a, tile0, blockIdx.x, red, rstd_sh, ssq_sh, pre0, pre1);
 }
 
 // The 8-row GEMV for K = 4096 with the rows' operand slice in REGISTERS and several tile groups per workgroup (round 6).  In k_gemv a workgroup
@@ -456,14 +502,15 @@ const char* ddk_last_gemv_kernel() { return g_last_kernel; }
 template <int EPI, int TILES>
 static void launch_gemv(const GemvArgs& a_, hipStream_t st) {
   const GemvArgs& a = a_;
-  NOTE_KERNEL("k_gemv<%d, %d, %d, 1, 1, %d, %d, %d>", EPI, TILES, a.fp8 ? 8 : (g_gemv_u == 4 || g_gemv_u == 16 ? g_gemv_u : 8), a.fp8 ? 1 : 0,
-              a.fp8 ? 0 : (g_gemv_pipe ? 1 : 0), a.fp8 ? 0 : (a.wf ? 1 : 0));
+  NOTE_KERNEL("k_gemv<%d, %d, %d, 1, 1, %d, %d, %d>", EPI, TILES, a.wq ? 8 : (g_gemv_u == 4 || g_gemv_u == 16 ? g_gemv_u : 8), a.wq,
+              a.wq ? 0 : (g_gemv_pipe ? 1 : 0), a.wq ? 0 : (a.wf ? 1 : 0));
 #define GV(U_, P_)                                                                             \
   do {                                                                                         \
     if (a.wf) k_gemv<EPI, TILES, U_, 1, 1, 0, P_, 1><<<a.n_tiles, GEMV_THREADS, 0, st>>>(a);   \
     else k_gemv<EPI, TILES, U_, 1, 1, 0, P_, 0><<<a.n_tiles, GEMV_THREADS, 0, st>>>(a);        \
   } while (0)
-  if (a.fp8) { k_gemv<EPI, TILES, 8, 1, 1, 1><<<a.n_tiles, GEMV_THREADS, 0, st>>>(a); return; }
+  if (a.wq == DD_WQ_MXFP4) { k_gemv<EPI, TILES, 8, 1, 1, DD_WQ_MXFP4><<<a.n_tiles, GEMV_THREADS, 0, st>>>(a); return; }
+  if (a.wq) { k_gemv<EPI, TILES, 8, 1, 1, DD_WQ_FP8><<<a.n_tiles, GEMV_THREADS, 0, st>>>(a); return; }
   const int u = g_gemv_u;
   if (g_gemv_pipe) { if (u == 4) GV(4, 1); else if (u == 16) GV(16, 1); else GV(8, 1); }
   else { if (u == 4) GV(4, 0); else if (u == 16) GV(16, 0); else GV(8, 0); }
@@ -483,9 +530,10 @@ static void launch_gemv_loop(const GemvArgs& a, int n_groups, hipStream_t st) {
 int ddk_gemv(int epi, const GemvArgs& a, hipStream_t st) {
   DD_REQUIRE(a.S % GEMV_WAVES == 0 && a.S >= GEMV_WAVES, "gemv: K=%d must be a multiple of 256", a.S * 32);
   DD_REQUIRE(a.nb >= 1 && a.nb <= 8, "gemv: nb=%d", a.nb);
-  DD_REQUIRE(!a.fp8 || a.wscale, "gemv: fp8 weights need row scales");
+  DD_REQUIRE(!a.wq || a.wscale, "gemv: fp8 / MXFP4 weights need their scales");
+  DD_REQUIRE(a.wq >= 0 && a.wq <= DD_WQ_MXFP4, "gemv: unknown weight storage %d", a.wq);
   DD_REQUIRE(!a.ssq_in || a.ssq_n >= 1, "gemv: ssq_n");
-  if (g_gemv_loop && !a.fp8 && a.S == 16 * GEMV_WAVES && a.n_tiles > 256 && (g_gemv_loop > 1 || a.n_tiles % 256 == 0)) {
+  if (g_gemv_loop && !a.wq && a.S == 16 * GEMV_WAVES && a.n_tiles > 256 && (g_gemv_loop > 1 || a.n_tiles % 256 == 0)) {
     // K = 4096 and a whole number of tile groups per CU: LLaMA-7B's qkv (768 tiles: 20.3 -> 19.2 us).  Measured and left on k_gemv: gate/up (688
     // tile pairs = 2.69 per workgroup, the third round two thirds empty: 34.0 -> 40.3 us); o_proj's 256 tiles are one group per workgroup either way
     // (dd_tools_set_tuning key 54 > 1 forces the form with that many workgroups for every K = 4096 matrix)
@@ -631,7 +679,7 @@ __device__ __forceinline__ void groups_epilogue(const GemvArgs& a, int wg, const
   }
 }
 
-template <int EPI, int TILES, int NG, int U = 4, int FP8 = 0, int WF = 0>
+template <int EPI, int TILES, int NG, int U = 4, int WQ = 0, int WF = 0>
 __global__ __launch_bounds__(GEMV_THREADS) void k_gemv_groups(GemvArgs a) {
   extern __shared__ float gg_sh[];
   float* red = gg_sh;                                   // [TILES * NG * 8 waves][256]
@@ -654,7 +702,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void k_gemv_groups(GemvArgs a) {
   // (round 6: the epilogue's operands and the rows' rstd are fetched AFTER the weight stream — groups_prefetch loads inside a divergent
   // branch and follows pointers, the compiler waits for those loads where they stand: in front of the first weight request, as in k_gemv)
 
-  if constexpr (FP8) {
+  if constexpr (WQ == DD_WQ_FP8) {
     // fp8 weights: one 1 KiB load = 64 k of a tile row = two MFMA k-steps, expanded exactly to bf16 in registers ONCE and
     // used for all NG operand planes; wave w takes 64-k steps w, w+8, ... (same order as k_gemv's fp8 path)
     const int S2 = S >> 1;
@@ -698,7 +746,50 @@ __global__ __launch_bounds__(GEMV_THREADS) void k_gemv_groups(GemvArgs a) {
       }
     }
   }
-  int s = FP8 ? spw : 0;
+  if constexpr (WQ == DD_WQ_MXFP4) {
+    // MXFP4 weights: one 1 KiB load = 128 k of a tile row = four MFMA k-steps, expanded ONCE and used for all NG operand planes;
+    // wave w takes 128-k loads w, w+8, ..., k-steps in order (k_gemv's MXFP4 path: the same chain per output)
+    const int S4 = S >> 2;
+    const u32x4_t* xq = a.xop + lane;
+    constexpr int UF = NG == 4 ? 1 : 2;
+    for (int s4 = wave; s4 < S4; s4 += GEMV_WAVES * UF) {
+      u32x4_t wf[TILES][UF], b[UF][4][NG];
+      uint32_t sc[TILES][UF];
+#pragma unroll
+      for (int u = 0; u < UF; ++u) {
+        int ss = s4 + u * GEMV_WAVES;
+        if (ss < S4) {
+#pragma unroll
+          for (int t = 0; t < TILES; ++t) {
+            wf[t][u] = __builtin_nontemporal_load(a.W + ((size_t)(tile0 + t) * S4 + ss) * 64 + lane);
+            sc[t][u] = ((const uint32_t*)a.wscale)[((size_t)(tile0 + t) * S4 + ss) * 16 + (lane & 15)];
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int g = 0; g < NG; ++g) b[u][j][g] = xq[(size_t)(4 * ss + j) * 64 + g * xplane];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < UF; ++u) {
+        int ss = s4 + u * GEMV_WAVES;
+        if (ss < S4) {
+#pragma unroll
+          for (int t = 0; t < TILES; ++t) {
+            u32x4_t k[4];
+            mxfp4x32_to_bf16(wf[t][u], sc[t][u], k);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+              for (int g = 0; g < NG; ++g)
+                acc[t][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, k[j]),
+                                                                    __builtin_bit_cast(bf16x8_t, b[u][j][g]), acc[t][g], 0, 0, 0);
+          }
+        }
+      }
+    }
+  }
+  int s = WQ ? spw : 0;
   for (; s + U <= spw; s += U) {
     u32x4_t b[U][NG], w[TILES][U];
 #pragma unroll
@@ -755,7 +846,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void k_gemv_groups(GemvArgs a) {
       const float* r = &red[((tt * NG + eg) * GEMV_WAVES + w) * 256];
       y += (r[o] + r[o + 32]) + (r[256 + o] + r[256 + o + 32]);
     }
-    if (FP8) y *= a.wscale[(size_t)(tile0 + tt) * 16 + n];
+    if (WQ == DD_WQ_FP8) y *= a.wscale[(size_t)(tile0 + tt) * 16 + n];   // (MXFP4: the block scales went in with the expansion)
     return y;
   };
   groups_epilogue<EPI, TILES, NG>(a, blockIdx.x, pre, rstd_sh, ssq_sh, tile_sum);
@@ -876,7 +967,7 @@ __global__ __launch_bounds__(32 * NG) void k_gemv_finish4(GemvArgs a, const floa
       for (int q = 0; q < NP; ++q) acc = acc + v[tt][q];
     }
     y[tt][0] = acc.x, y[tt][1] = acc.y, y[tt][2] = acc.z, y[tt][3] = acc.w;
-    if (a.fp8 && EPI != EPI_RESID) {         // fp8 tiles: the output rows' scales, after the sum as in k_gemv
+    if (a.wq == DD_WQ_FP8 && EPI != EPI_RESID) {         // fp8 tiles: the output rows' scales, after the sum as in k_gemv
       const f32x4_t sc = *(const f32x4_t*)&a.wscale[(size_t)(tile0 + tt) * 16 + n0];
       y[tt][0] *= sc.x, y[tt][1] *= sc.y, y[tt][2] *= sc.z, y[tt][3] *= sc.w;
     }
@@ -902,11 +993,11 @@ __global__ __launch_bounds__(32 * NG) void k_gemv_finish4(GemvArgs a, const floa
       // fp8 tiles: x + scale * sum as ONE fused multiply-add — the form the 8-row kernel's epilogue compiles to (its scale multiply
       // and residual add contract), which the rows of every pass width must reproduce
       f32x4_t sc4 = {1.f, 1.f, 1.f, 1.f};
-      if (a.fp8) sc4 = *(const f32x4_t*)&a.wscale[(size_t)tile0 * 16 + n0];
+      if (a.wq == DD_WQ_FP8) sc4 = *(const f32x4_t*)&a.wscale[(size_t)tile0 * 16 + n0];
       const float sc[4] = {sc4.x, sc4.y, sc4.z, sc4.w};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        xn[i] = a.fp8 ? __builtin_fmaf(y[0][i], sc[i], p0[i]) : p0[i] + y[0][i];
+        xn[i] = a.wq == DD_WQ_FP8 ? __builtin_fmaf(y[0][i], sc[i], p0[i]) : p0[i] + y[0][i];
         z[i] = p1[i] * xn[i];
         sq[i] = xn[i] * xn[i];
       }
@@ -978,7 +1069,7 @@ __global__ __launch_bounds__(32 * NG) void k_gemv_finish4(GemvArgs a, const floa
   }
 }
 
-template <int EPI, int TILES, int NG, int FP8>
+template <int EPI, int TILES, int NG, int WQ>
 static int launch_gemv_groups_f(const GemvArgs& a, hipStream_t st) {
   size_t smem = (size_t)(TILES * NG * GEMV_WAVES * 256 + 8 * NG + 16 * 8 * NG) * sizeof(float);
   // weight tiles requested per wave before the first MFMA: 4; 2 for the two-tile kernels with four operand planes (keeps
@@ -987,18 +1078,19 @@ static int launch_gemv_groups_f(const GemvArgs& a, hipStream_t st) {
   constexpr int U = (TILES == 2 && NG == 4) ? 2 : (EPI == EPI_RESID ? 8 : 4);
   static bool attr = false;
   if (!attr && smem > 48 * 1024) {
-    DD_HIP(hipFuncSetAttribute((const void*)k_gemv_groups<EPI, TILES, NG, U, FP8, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    if (!FP8) DD_HIP(hipFuncSetAttribute((const void*)k_gemv_groups<EPI, TILES, NG, U, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    DD_HIP(hipFuncSetAttribute((const void*)k_gemv_groups<EPI, TILES, NG, U, WQ, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    if (!WQ) DD_HIP(hipFuncSetAttribute((const void*)k_gemv_groups<EPI, TILES, NG, U, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     attr = true;
   }
-  NOTE_KERNEL("k_gemv_groups<%d, %d, %d, %d, %d, %d>", EPI, TILES, NG, U, FP8, (!FP8 && a.wf) ? 1 : 0);
-  if (!FP8 && a.wf) k_gemv_groups<EPI, TILES, NG, U, 0, 1><<<a.n_tiles, GEMV_THREADS, smem, st>>>(a);
-  else k_gemv_groups<EPI, TILES, NG, U, FP8, 0><<<a.n_tiles, GEMV_THREADS, smem, st>>>(a);
+  NOTE_KERNEL("k_gemv_groups<%d, %d, %d, %d, %d, %d>", EPI, TILES, NG, U, WQ, (!WQ && a.wf) ? 1 : 0);
+  if (!WQ && a.wf) k_gemv_groups<EPI, TILES, NG, U, 0, 1><<<a.n_tiles, GEMV_THREADS, smem, st>>>(a);
+  else k_gemv_groups<EPI, TILES, NG, U, WQ, 0><<<a.n_tiles, GEMV_THREADS, smem, st>>>(a);
   return DD_OK;
 }
 template <int EPI, int TILES, int NG>
 static int launch_gemv_groups(const GemvArgs& a, hipStream_t st) {
-  return a.fp8 ? launch_gemv_groups_f<EPI, TILES, NG, 1>(a, st) : launch_gemv_groups_f<EPI, TILES, NG, 0>(a, st);
+  if (a.wq == DD_WQ_MXFP4) return launch_gemv_groups_f<EPI, TILES, NG, DD_WQ_MXFP4>(a, st);
+  return a.wq ? launch_gemv_groups_f<EPI, TILES, NG, DD_WQ_FP8>(a, st) : launch_gemv_groups_f<EPI, TILES, NG, 0>(a, st);
 }
 
 // ---- slice-resident path (dd_gemv_slices.h + k_gemv_finish): bf16 weights, the per-layer matrices at the shapes the 7B
@@ -1087,7 +1179,7 @@ int g_finish4 = 15;   // dd_tools_set_tuning key 24: the four-columns-per-thread
 template <int EPI, int TILES, int NG, int NP>
 static void launch_finish(const GemvArgs& a, int n_sets, hipStream_t st) {
   if (g_slices_only) return;
-  if ((g_finish4 & (1 << EPI)) || a.fp8) k_gemv_finish4<EPI, TILES, NG, NP><<<n_sets, 32 * NG, 0, st>>>(a, a.part, a.part + a.part_floats, n_sets);
+  if ((g_finish4 & (1 << EPI)) || a.wq == DD_WQ_FP8) k_gemv_finish4<EPI, TILES, NG, NP><<<n_sets, 32 * NG, 0, st>>>(a, a.part, a.part + a.part_floats, n_sets);
   else k_gemv_finish<EPI, TILES, NG, NP><<<n_sets, 128 * NG, 0, st>>>(a, a.part, a.part + a.part_floats, n_sets);
 }
 template <int NG, int SPW2, int CH, int UW>
@@ -1161,7 +1253,8 @@ static int try_slices_fp8(int epi, const GemvArgs& a, hipStream_t st) {
 
 template <int NG>
 static int try_slices(int epi, const GemvArgs& a, hipStream_t st) {
-  if (a.fp8) return try_slices_fp8<NG>(epi, a, st);
+  if (a.wq == DD_WQ_MXFP4) return SLICES_UNSUPPORTED;     // no slice kernels for MXFP4 tiles: k_gemv_groups (64 rows: two 32-row passes)
+  if (a.wq) return try_slices_fp8<NG>(epi, a, st);
   const int spw = a.S / GEMV_WAVES;
   const int nt = epi == EPI_SILU ? 2 * a.n_tiles : a.n_tiles;      // 16-row weight tiles
   if (!(spw == 16 || spw == 43 || spw == 56) || nt < 64) return SLICES_UNSUPPORTED;
@@ -1308,7 +1401,8 @@ static int try_slices9_fp8(int epi, const GemvArgs& a, hipStream_t st) {
   return DD_OK;
 }
 static int try_slices9(int epi, const GemvArgs& a, hipStream_t st) {
-  if (a.fp8) return try_slices9_fp8(epi, a, st);
+  if (a.wq == DD_WQ_MXFP4) return SLICES_UNSUPPORTED;
+  if (a.wq) return try_slices9_fp8(epi, a, st);
   const int spw = a.S / GEMV_WAVES;
   const int nt = epi == EPI_SILU ? 2 * a.n_tiles : a.n_tiles;
   if (!(spw == 16 || spw == 43 || spw == 56) || nt < 64) return SLICES_UNSUPPORTED;
@@ -1397,13 +1491,14 @@ static int try_slices9(int epi, const GemvArgs& a, hipStream_t st) {
 int ddk_gemv_groups(int epi, const GemvArgs& a, hipStream_t st) {
   DD_REQUIRE(a.S % GEMV_WAVES == 0 && a.S >= GEMV_WAVES, "gemv_groups: K=%d must be a multiple of 256", a.S * 32);
   DD_REQUIRE(a.nb >= 1 && a.nb <= 8, "gemv_groups: nb=%d rows per group", a.nb);
-  DD_REQUIRE(!a.fp8 || a.wscale, "gemv_groups: fp8 weights need row scales");
+  DD_REQUIRE(!a.wq || a.wscale, "gemv_groups: fp8 / MXFP4 weights need their scales");
+  DD_REQUIRE(a.wq >= 0 && a.wq <= DD_WQ_MXFP4, "gemv_groups: unknown weight storage %d", a.wq);
   DD_REQUIRE(a.n_groups == 2 || a.n_groups == 4 || a.n_groups == 8 || a.n_groups == 9, "gemv_groups: %d groups (2, 4, 8 or 9)", a.n_groups);
-  DD_REQUIRE(!a.half_planes || (((a.n_groups == 8 && a.half_planes == 8) || (a.n_groups == 9 && a.half_planes == 7)) && a.nb <= 4 && !a.fp8 && a.part && g_gemv_slices),
+  DD_REQUIRE(!a.half_planes || (((a.n_groups == 8 && a.half_planes == 8) || (a.n_groups == 9 && a.half_planes == 7)) && a.nb <= 4 && !a.wq && a.part && g_gemv_slices),
              "gemv_groups: half planes take an eight- or nine-plane pass of 16-bit weights, K <= 4");
   if (a.n_groups == 9) {
     int rs = a.part ? try_slices9(epi, a, st) : SLICES_UNSUPPORTED;
-    DD_REQUIRE(rs != SLICES_UNSUPPORTED, "gemv_groups: no nine-plane kernel for this matrix (K = %d, %d tiles, fp8 %d)", a.S * 32, a.n_tiles, a.fp8);
+    DD_REQUIRE(rs != SLICES_UNSUPPORTED, "gemv_groups: no nine-plane kernel for this matrix (K = %d, %d tiles, weight storage %d)", a.S * 32, a.n_tiles, a.wq);
     if (rs != DD_OK) return rs;
     DD_CHECK_LAUNCH();
     return DD_OK;

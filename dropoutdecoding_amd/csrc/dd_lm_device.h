@@ -28,6 +28,24 @@ __device__ __forceinline__ void fp8x16_to_bf16(u32x4_t w, u32x4_t& k0, u32x4_t& 
   k1 = (u32x4_t){o[4], o[5], o[6], o[7]};
 }
 
+// MXFP4 (OCP e2m1 elements, one e8m0 scale per 32 k) x32 -> four bf16x8 MFMA operands, exact: an e2m1 value has one
+// mantissa bit and the scale is a power of two, so every product with a scale byte in [7, 247] is a normal bf16.  w[j] holds
+// the 8 elements of k-step j (element 2 i in the low nibble of byte i), byte j of sc the scale of that k-step: gfx950's
+// v_cvt_scalef32_pk_bf16_fp4 turns one byte into a scaled bf16 pair, low nibble into the low half — 16 VALU ops per KiB.
+__device__ __forceinline__ void mxfp4x32_to_bf16(u32x4_t w, uint32_t sc, u32x4_t (&k)[4]) {
+  typedef __attribute__((ext_vector_type(2))) __bf16 bf2_t;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float s = __builtin_bit_cast(float, ((sc >> (8 * j)) & 0xffu) << 23);   // 2^(b - 127)
+    bf2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w[j], s, 0);
+    bf2_t p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w[j], s, 1);
+    bf2_t p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w[j], s, 2);
+    bf2_t p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w[j], s, 3);
+    k[j] = (u32x4_t){__builtin_bit_cast(uint32_t, p0), __builtin_bit_cast(uint32_t, p1), __builtin_bit_cast(uint32_t, p2),
+                     __builtin_bit_cast(uint32_t, p3)};
+  }
+}
+
 // write the hi/lo split of value y for (row m, k index k) into a packed decode operand
 __device__ __forceinline__ void xop_store(u32x4_t* xop, int k, int m, float y, int wf = 0) {
   uint32_t hi, lo;

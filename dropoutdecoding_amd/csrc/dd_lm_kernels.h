@@ -95,10 +95,26 @@ int ddk_pack_weight_fp8(const uint8_t* src_dev, const float* row_scale_dev, int 
 int ddk_dequant_tiles(const u32x4_t* src_fp8, u32x4_t* dst_bf16, int n_tiles, int S, hipStream_t st);
 int ddk_fill_synthetic_fp8(uint8_t* dst, size_t n, uint32_t seed, hipStream_t st);
 
+// MXFP4 weight storage (OCP Microscaling: e2m1 elements, one e8m0 scale byte 2^(b - 127) per 32 consecutive k of a row):
+// tile (nt, s4) = 64 lanes x 16 bytes at ((nt*S4 + s4)*64 + lane), S4 = K/128; lane (g<<4)|r holds four u32, word j = the 8
+// elements W[row][s4*128 + 32 j + 8 g ..+7] (element 2 i in the low nibble of byte i): one 1 KiB wave load feeds FOUR bf16
+// MFMA k-steps after an exact in-register expansion (mxfp4x32_to_bf16), word j being the lane's A fragment of k-step j.
+// Scales: u32 [(nt*S4 + s4)*16 + r], byte j = the e8m0 byte of row r's block 4 s4 + j — 64 B per KiB of elements, the four
+// lanes of a row read one word; applied during the expansion, nothing is left for the epilogue.  0.5 + 1/32 bytes per parameter.
+// *bad_scale (device) is set when a scale byte of a live row lies outside [7, 247].
+int ddk_pack_weight_mxfp4(const uint8_t* src_dev, const uint8_t* scale_dev, int rows, int cols, u32x4_t* dst, uint32_t* dst_scale,
+                          int dst_tile0, int tile_stride, int pack_mode, int n_src_tiles, int32_t* bad_scale, hipStream_t st);
+// MXFP4 tiles -> bf16 tiles of the plain layout with the scales applied (prefill GEMM operand, wscale = nullptr)
+int ddk_dequant_tiles_mxfp4(const u32x4_t* src, const uint32_t* scales, u32x4_t* dst_bf16, int n_tiles, int S, hipStream_t st);
+int ddk_fill_synthetic_mxfp4(uint8_t* dst, size_t n, uint32_t seed, hipStream_t st);     // random codes: every byte is two valid elements
+int ddk_fill_const_u32(uint32_t* dst, size_t n, uint32_t v, hipStream_t st);
+#define DD_WQ_FP8 1
+#define DD_WQ_MXFP4 2
+
 struct GemvArgs {
   const u32x4_t* W;
-  int fp8;              // 1: W holds fp8 tiles (S2 = S/2 per tile row), wscale required
-  const float* wscale;  // [tiles*16] per-row scales in packed-row order (fp8) or nullptr
+  int wq;               // storage of W: 0 16-bit tiles, DD_WQ_FP8 fp8 tiles (S/2 per tile row), DD_WQ_MXFP4 MXFP4 tiles (S/4 per tile row); wscale required for both
+  const float* wscale;  // fp8: [tiles*16] per-row scales in packed-row order; MXFP4: the u32 block-scale words [tiles][S/4][16]; else nullptr
   int S;                // K / 32
   int n_tiles;          // number of 16-row tiles (EPI_SILU: number of gate/up PAIRS)
   int nb;               // live rows (1..8)

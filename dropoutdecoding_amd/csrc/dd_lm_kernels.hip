@@ -109,6 +109,79 @@ int ddk_dequant_tiles(const u32x4_t* src, u32x4_t* dst, int n_tiles, int S, hipS
   return DD_OK;
 }
 
+// MXFP4: [rows][cols/2] bytes + [rows][cols/32] e8m0 bytes -> streaming tiles + scale words (layout: dd_lm_kernels.h).  The source
+// keeps element 2 j in the low nibble of byte j, which is the order v_cvt_scalef32_pk_bf16_fp4 emits: the 8 elements of one k-step
+// are one aligned u32 of the source row, the four scale bytes of a 128-k load one aligned u32 of the scale row.
+__global__ __launch_bounds__(256) void k_pack_weight_mxfp4(const uint8_t* __restrict__ src, const uint8_t* __restrict__ sc,
+                                                           int rows, int cols, u32x4_t* __restrict__ dst,
+                                                           uint32_t* __restrict__ dscale, int dst_tile0, int tile_stride,
+                                                           int pack_mode, int n_src_tiles, int32_t* __restrict__ bad_scale) {
+  int S4 = cols >> 7;
+  size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+  size_t total = (size_t)n_src_tiles * S4 * 64;
+  if (gid >= total) return;
+  int lane = (int)(gid & 63);
+  size_t q = gid >> 6;
+  int s4 = (int)(q % S4);
+  int nt = (int)(q / S4);
+  int g = lane >> 4, r = lane & 15;
+  int row;
+  if (pack_mode == PACK_ROPE) {
+    int head = nt >> 3, tt = nt & 7;
+    row = head * HEAD_DIM + (r < 8 ? tt * 8 + r : ROPE_HALF + tt * 8 + (r - 8));
+  } else {
+    row = nt * 16 + r;
+  }
+  u32x4_t v = {0u, 0u, 0u, 0u};
+  if (row < rows) {
+    const uint32_t* p = (const uint32_t*)(src + (size_t)row * (cols >> 1) + (size_t)s4 * 64) + g;   // k = 128 s4 + 32 j + 8 g: word 4 j + g
+    v = (u32x4_t){p[0], p[4], p[8], p[12]};
+  }
+  int dt = dst_tile0 + nt * tile_stride;
+  dst[((size_t)dt * S4 + s4) * 64 + lane] = v;
+  if (g == 0) {
+    uint32_t w = 0x7f7f7f7fu;                        // rows past the matrix (vocabulary padding): zero elements, scale 1
+    if (row < rows) {
+      w = *(const uint32_t*)(sc + (size_t)row * (cols >> 5) + (size_t)s4 * 4);
+      bool bad = false;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t b = (w >> (8 * j)) & 0xffu;
+        bad |= b < 7u || b > 247u;
+      }
+      if (bad) *bad_scale = 1;
+    }
+    dscale[((size_t)dt * S4 + s4) * 16 + r] = w;
+  }
+}
+int ddk_pack_weight_mxfp4(const uint8_t* src, const uint8_t* sc, int rows, int cols, u32x4_t* dst, uint32_t* dscale, int dst_tile0,
+                          int tile_stride, int pack_mode, int n_src_tiles, int32_t* bad_scale, hipStream_t st) {
+  DD_REQUIRE(cols % 128 == 0, "pack_weight_mxfp4: K=%d must be a multiple of 128", cols);
+  size_t total = (size_t)n_src_tiles * (cols >> 7) * 64;
+  k_pack_weight_mxfp4<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(src, sc, rows, cols, dst, dscale, dst_tile0, tile_stride,
+                                                                       pack_mode, n_src_tiles, bad_scale);
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
+__global__ __launch_bounds__(256) void k_dequant_tiles_mxfp4(const u32x4_t* __restrict__ src, const uint32_t* __restrict__ sc,
+                                                             u32x4_t* __restrict__ dst, size_t total) {
+  size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= total) return;
+  int lane = (int)(gid & 63);
+  size_t q = gid >> 6;                               // nt * S4 + s4: four bf16 k-steps 4 q .. 4 q + 3 of the plain layout
+  u32x4_t k[4];
+  mxfp4x32_to_bf16(src[gid], sc[q * 16 + (lane & 15)], k);
+  size_t o = q * 4 * 64 + lane;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) dst[o + (size_t)j * 64] = k[j];
+}
+int ddk_dequant_tiles_mxfp4(const u32x4_t* src, const uint32_t* scales, u32x4_t* dst, int n_tiles, int S, hipStream_t st) {
+  size_t total = (size_t)n_tiles * (S >> 2) * 64;
+  k_dequant_tiles_mxfp4<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(src, scales, dst, total);
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
+
 __device__ __forceinline__ uint32_t hash32(uint32_t x) {
   x ^= x >> 16;
   x *= 0x7feb352du;
@@ -138,6 +211,27 @@ __global__ __launch_bounds__(256) void k_fill_synth_fp8(uint8_t* dst, size_t n, 
 }
 int ddk_fill_synthetic_fp8(uint8_t* dst, size_t n, uint32_t seed, hipStream_t st) {
   k_fill_synth_fp8<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(dst, n, seed);
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
+// random e2m1 pairs: every byte is valid (no NaN / Inf encodings in e2m1)
+__global__ __launch_bounds__(256) void k_fill_synth_mxfp4(uint8_t* dst, size_t n, uint32_t seed) {
+  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  uint32_t h = hash32((uint32_t)i * 0x9e3779b9u + seed) ^ hash32((uint32_t)(i >> 32) + seed * 31u);
+  dst[i] = (uint8_t)(h & 0xff);
+}
+int ddk_fill_synthetic_mxfp4(uint8_t* dst, size_t n, uint32_t seed, hipStream_t st) {
+  k_fill_synth_mxfp4<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(dst, n, seed);
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
+__global__ void k_fill_const_u32(uint32_t* dst, size_t n, uint32_t v) {
+  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) dst[i] = v;
+}
+int ddk_fill_const_u32(uint32_t* dst, size_t n, uint32_t v, hipStream_t st) {
+  k_fill_const_u32<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(dst, n, v);
   DD_CHECK_LAUNCH();
   return DD_OK;
 }

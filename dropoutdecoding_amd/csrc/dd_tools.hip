@@ -52,7 +52,7 @@ extern "C" int dd_lm_time_gemv(dd_lm* h, int which, int nb, int iters, float* me
     GemvArgs a;
     memset(&a, 0, sizeof(a));
     a.wf = h->wf;
-    a.nb = nb, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps, a.state = h->state, a.fp8 = h->fp8;
+    a.nb = nb, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps, a.state = h->state, a.wq = h->wq;
     switch (which) {
       case 0:
         a.W = w.wqkv, a.wscale = w.s_qkv, a.S = h->S_d, a.n_tiles = h->qkv_tiles, a.xop = h->xop_d, a.ssq_in = h->ssq_a, a.ssq_n = d / 16, a.ssq_ld = d / 16;
@@ -82,7 +82,7 @@ extern "C" int dd_lm_time_gemv(dd_lm* h, int which, int nb, int iters, float* me
   DD_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
   *mean_ms = ms / iters;
   double rows[4] = {(double)(h->q_dim + 2 * h->kv_dim) * d, (double)d * h->q_dim, 2.0 * dff * d, (double)d * dff};
-  *bytes_per_launch = rows[which] * (h->fp8 ? 1.0 : 2.0);
+  *bytes_per_launch = rows[which] * (h->wq == DD_WQ_MXFP4 ? 0.5 + 1.0 / 32.0 : (h->wq ? 1.0 : 2.0));
   return DD_OK;
 }
 

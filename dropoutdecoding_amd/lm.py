@@ -95,6 +95,42 @@ def dequantize_fp8(q_u8: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return q_u8.view(torch.float8_e4m3fn).float() * scale[:, None]
 
 
+_WEIGHT_FORMATS = {"bf16": 0, "fp8": 1, "fp16": 2, "mxfp4": 3}      # dd_lm_config.weight_format
+_E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)       # OCP e2m1 magnitudes by code (2 exponent bits, 1 mantissa bit)
+
+
+def quantize_mxfp4(w: torch.Tensor):
+    """OCP Microscaling MXFP4 along K: every block of 32 consecutive elements of a row shares one e8m0 scale 2^e,
+    e = clamp(floor(log2(max|w|)) - 2, -120, 120) (an all-zero block: -120), so that the block maximum lands in [4, 8) — the top
+    binade of e2m1.  Elements are w / 2^e rounded to the nearest e2m1 value (+-{0, 0.5, 1, 1.5, 2, 3, 4, 6}), ties to the even
+    code, magnitudes above 6 saturate to 6, the sign is kept.  Returns (q_packed uint8 [N, K/2]: element 2j in the low nibble
+    of byte j, scale uint8 [N, K/32]: e + 127).  Build-defined (the reference has no 4-bit path)."""
+    if w.dim() != 2 or w.shape[1] % 32:
+        raise ValueError(f"quantize_mxfp4: a matrix [N, K] with K a multiple of 32, got {tuple(w.shape)}")
+    n, k = w.shape
+    wf = w.detach().float().reshape(n, k // 32, 32)
+    amax = wf.abs().amax(dim=2)
+    _, ex = torch.frexp(amax)                                    # amax = m * 2^ex, m in [0.5, 1): floor(log2(amax)) = ex - 1
+    e = torch.where(amax > 0, ex.to(torch.int32) - 3, torch.full_like(ex, -120, dtype=torch.int32)).clamp(-120, 120)
+    a = torch.ldexp(wf.abs(), -e[:, :, None])                    # exact: a power-of-two scaling
+    # code = number of midpoints passed; at a midpoint the even code wins (0.25 -> 0, 0.75 -> 1.0, 1.25 -> 1.0, 1.75 -> 2.0,
+    # 2.5 -> 2.0, 3.5 -> 4.0, 5.0 -> 4.0)
+    code = ((a > 0.25).to(torch.uint8) + (a >= 0.75).to(torch.uint8) + (a > 1.25).to(torch.uint8) + (a >= 1.75).to(torch.uint8) +
+            (a > 2.5).to(torch.uint8) + (a >= 3.5).to(torch.uint8) + (a > 5.0).to(torch.uint8))
+    code = (code | (torch.signbit(wf).to(torch.uint8) << 3)).reshape(n, k)
+    q = (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
+    return q, (e + 127).to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4(q_packed: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """fp32 [N, K] of an MXFP4 matrix (quantize_mxfp4's layout); every value is exactly representable in bf16."""
+    n, k2 = q_packed.shape
+    lut = torch.tensor(_E2M1_VALUES + tuple(-v for v in _E2M1_VALUES), dtype=torch.float32, device=q_packed.device)
+    codes = torch.stack((q_packed & 15, q_packed >> 4), dim=2).reshape(n, 2 * k2).long()
+    e = scale.to(torch.int32) - 127
+    return torch.ldexp(lut[codes].reshape(n, k2 // 16, 32), e[:, :, None]).reshape(n, 2 * k2)
+
+
 class DropoutEngine:
     def __init__(self, cfg: LMConfig, family: str = FAMILY_LLAVA, max_seq: int = 1280, max_visual: int = 576,
                  seed: Optional[int] = None, use_random: bool = False, device: Optional[torch.device] = None,
@@ -105,6 +141,10 @@ class DropoutEngine:
         intermediate size (tp_local_config) and the engine is driven through TensorParallelGroup / dist.TensorParallelRank."""
         if family not in _FAMILY:
             raise ValueError(f"unknown family {family!r}")
+        if weight_format not in _WEIGHT_FORMATS:
+            raise ValueError(f"weight_format {weight_format!r}: one of {sorted(_WEIGHT_FORMATS)}")
+        if tp is not None and weight_format == "mxfp4":
+            raise ValueError("tensor-parallel shards keep 16-bit matrices: weight_format 'mxfp4' cannot be combined with tp=")
         if not torch.cuda.is_available():
             raise _lib.DDError("DropoutEngine needs a GPU (MI355X); there is no CPU fallback for the product path")
         # lib: another instance of the library than the process's (bench.py's roofline leg: _lib.load_tools())
@@ -138,7 +178,7 @@ class DropoutEngine:
         c = _lib.LMConfigC(cfg.vocab_size, cfg.hidden_size, cfg.intermediate_size, cfg.num_layers, cfg.num_heads,
                            cfg.num_kv_heads, cfg.head_dim, cfg.rms_eps, cfg.rope_theta, max_seq, max_visual,
                            fam["k_top"], fam["mask_mode"], fam["vote_on"], fam["leak_mask"],
-                           {"bf16": 0, "fp8": 1, "fp16": 2}[weight_format], {"fp32": 0, "fp16": 1}[kv_format])
+                           _WEIGHT_FORMATS[weight_format], {"fp32": 0, "fp16": 1}[kv_format])
         self.tp = tp
         if tp is not None:
             c.reserved[0], c.reserved[1] = int(tp[1]), int(tp[0])
@@ -194,12 +234,18 @@ class DropoutEngine:
         self._ck(self.lib.dd_lm_load_tensor_fp8(self._h, tid, layer, q.data_ptr(), s.data_ptr(), q.shape[0], q.shape[1],
                                                   1 if q.is_cuda else 0), f"dd_lm_load_tensor_fp8({tid},{layer})")
 
+    def _load_mxfp4(self, tid: int, layer: int, t: torch.Tensor) -> None:
+        q, s = quantize_mxfp4(t.detach())
+        self._ck(self.lib.dd_lm_load_tensor_mxfp4(self._h, tid, layer, q.data_ptr(), s.data_ptr(), t.shape[0], t.shape[1],
+                                                    1 if q.is_cuda else 0), f"dd_lm_load_tensor_mxfp4({tid},{layer})")
+
     def load_state_dict(self, sd: Dict[str, torch.Tensor], prefix: str = "") -> None:
         """HF LlamaForCausalLM / MistralForCausalLM parameter names (optionally under `prefix`).  An fp8 engine
-        quantises every matrix with `quantize_fp8` (per-row absmax / 448, OCP e4m3fn) on the way in; a bf16 engine rounds to
+        quantises every matrix with `quantize_fp8` (per-row absmax / 448, OCP e4m3fn) on the way in, an MXFP4 engine with
+        `quantize_mxfp4` (e2m1 elements, one power-of-two scale per 32 k; embedding and norm vectors stay bf16); a bf16 engine rounds to
         bf16 (exact for bf16 checkpoints), an fp16 engine to fp16 (exact for the fp16 checkpoints the reference loads)."""
         g = lambda k: sd[prefix + k]
-        mat = self._load_fp8 if self.weight_format == "fp8" else self._load
+        mat = {"fp8": self._load_fp8, "mxfp4": self._load_mxfp4}.get(self.weight_format, self._load)
         self._load(T_EMBED, 0, g("model.embed_tokens.weight"))
         self._load(T_FINAL_NORM, 0, g("model.norm.weight"))
         mat(T_LM_HEAD, 0, g("lm_head.weight"))

@@ -190,7 +190,10 @@ typedef struct dd_lm_config {
                                 2 = fp16 matrices / embeddings / norm vectors: fp16-native checkpoints (every model the reference
                                 loads: chair_test/chair_test.py:189-213, torch_dtype=float16) stay EXACT instead of losing three
                                 mantissa bits in a cast to bf16; activations are then split hi + lo in fp16 (~22 mantissa bits) and
-                                every weight product runs on v_mfma_f32_16x16x32_f16 */
+                                every weight product runs on v_mfma_f32_16x16x32_f16,
+                                3 = OCP Microscaling MXFP4 matrices: e2m1 elements with one e8m0 scale byte per 32 consecutive k of a
+                                row (0.5 + 1/32 bytes per parameter), expanded exactly to bf16 in registers; embedding and norm
+                                vectors stay bf16 (dd_lm_load_tensor_mxfp4) */
   int32_t kv_format;         /* KV cache storage: 0 = fp32 (default), 1 = fp16 — the width the reference keeps its cache in
                                 (chair_test/chair_test.py:189-213: torch_dtype=float16): half the attention bytes; K/V are
                                 rounded to nearest-even when they enter the cache, attention arithmetic stays fp32 */
@@ -220,7 +223,7 @@ int dd_lm_destroy(dd_lm* h);
 size_t dd_lm_device_bytes(const dd_lm* h);
 
 /* Copy one HF-layout 16-bit tensor (row-major, `rows` x `cols`) into the engine and re-tile it
- * for MFMA streaming: bf16 bits for engines of weight_format 0 (and the embedding / norm vectors of fp8 engines), fp16 bits
+ * for MFMA streaming: bf16 bits for engines of weight_format 0 (and the embedding / norm vectors of fp8 and MXFP4 engines), fp16 bits
  * for weight_format 2.  src may be a host or a device pointer (src_on_device).  Synchronous. */
 int dd_lm_load_tensor(dd_lm* h, int tensor_id, int layer, const uint16_t* src_bf16, int rows, int cols,
                       int src_on_device);
@@ -230,6 +233,20 @@ int dd_lm_load_tensor(dd_lm* h, int tensor_id, int layer, const uint16_t* src_bf
  * through dd_lm_load_tensor. */
 int dd_lm_load_tensor_fp8(dd_lm* h, int tensor_id, int layer, const uint8_t* q_e4m3, const float* row_scale, int rows,
                           int cols, int src_on_device);
+/* MXFP4 engines (weight_format 3): one matrix as e2m1 codes (1 sign, 2 exponent, 1 mantissa bit: +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}),
+ * q_packed [rows][cols/2] with element 2j in the low nibble of byte j, plus scale_e8m0 [rows][cols/32]: byte b scales the 32
+ * elements of its block by 2^(b - 127).  W = scale * element is exactly representable in bf16; the kernels expand it in registers
+ * and run the bf16 MFMA against the hi/lo-split activations, so the engine computes "fp32 activations x the dequantised matrix".
+ * Same tensor ids as dd_lm_load_tensor_fp8.  DD_EINVAL for a non-matrix id, a wrong shape, an engine of another weight_format, a
+ * handle that borrows its weights, or a scale byte outside [7, 247] (exponents -120..120 keep every product a normal bf16; the
+ * tensor's tiles are then undefined until it is loaded again).  Quantisation policy is the caller's
+ * (dropoutdecoding_amd.lm.quantize_mxfp4).  Embedding and norm vectors go through dd_lm_load_tensor (bf16).  Synchronous.
+ * Covered: prefill / prefill_group / prefill_extend (both paths) / prefill_ensemble, decode steps under every speculation policy,
+ * dd_lm_group_step in its classic form for 1..64 lanes (16 / 32 rows: the grouped GEMV; 64 rows: two 32-row passes), generation
+ * records, the EOS stop, both KV formats, K up to 64.  Not covered: the rider and half-plane group forms (never chosen for this
+ * format: the classic form runs instead) and tensor-parallel shards (dd_lm_create refuses them, as for fp8). */
+int dd_lm_load_tensor_mxfp4(dd_lm* h, int tensor_id, int layer, const uint8_t* q_packed, const uint8_t* scale_e8m0, int rows,
+                            int cols, int src_on_device);
 
 /* Fill every weight with a deterministic pseudo-random bf16 pattern of the given scale
  * (synthetic-weights benchmark mode; no host traffic). */
