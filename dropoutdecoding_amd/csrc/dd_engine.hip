@@ -134,7 +134,6 @@ static int lm_create_impl(const dd_lm_config* c, dd_lm* parent, dd_lm** out) {
   h->kv16 = c->kv_format == 1 ? 1 : 0;
   DD_REQUIRE(c->kv_format == 0 || c->kv_format == 1, "dd_lm_create: unknown KV cache format %d", c->kv_format);
   DD_REQUIRE(c->weight_format >= 0 && c->weight_format <= 3, "dd_lm_create: unknown weight format %d", c->weight_format);
-  const int wdiv = h->wq == DD_WQ_MXFP4 ? 4 : (h->wq ? 2 : 1);   // u32x4 units per tile row: S*64 (bf16), (S/2)*64 (fp8) or (S/4)*64 (MXFP4)
   if (parent) {
     // a lane: another sequence over the SAME weights (its own KV cache, state and scratch)
     const dd_lm_config& pc = parent->cfg;
@@ -151,29 +150,23 @@ static int lm_create_impl(const dd_lm_config* c, dd_lm* parent, dd_lm** out) {
     h->final_norm = parent->final_norm, h->embed = parent->embed;
   } else {
   h->lw.resize(h->Lyr);
+  size_t mx = 0;                 // the largest matrix, in tile rows x S: what deq_tmp must hold
   for (int l = 0; l < h->Lyr; ++l) {
     LayerW& w = h->lw[l];
-    DA(w.wqkv, (size_t)h->qkv_tiles * h->S_d * 64 / wdiv);
-    DA(w.wo, (size_t)(d / 16) * h->S_q * 64 / wdiv);
-    DA(w.wgu, (size_t)(2 * dff / 16) * h->S_d * 64 / wdiv);
-    DA(w.wdown, (size_t)(d / 16) * h->S_ff * 64 / wdiv);
-    if (h->wq) {       // fp8: one float per row; MXFP4: one u32 (four e8m0 bytes) per row and 128 k
-      const size_t md = h->wq == DD_WQ_MXFP4 ? h->S_d / 4 : 1, mq = h->wq == DD_WQ_MXFP4 ? h->S_q / 4 : 1, mf = h->wq == DD_WQ_MXFP4 ? h->S_ff / 4 : 1;
-      DA(w.s_qkv, (size_t)h->qkv_tiles * 16 * md);
-      DA(w.s_o, (size_t)d * mq);
-      DA(w.s_gu, (size_t)2 * dff * md);
-      DA(w.s_down, (size_t)d * mf);
+    for (int k = DD_M_QKV; k <= DD_M_DOWN; ++k) {
+      const WMat m = dd_weight(h, l, k);
+      DA(w.w[k], dd_weight_units(h, m));
+      if ((size_t)m.n_tiles * m.S > mx) mx = (size_t)m.n_tiles * m.S;
     }
+    for (int k = DD_M_QKV; k <= DD_M_DOWN && h->wq; ++k) DA(w.s[k], dd_weight_scales(h, dd_weight(h, l, k)));
     DA(w.norm1, d);
     DA(w.norm2, d);
   }
-  DA(h->lm_head, (size_t)(h->Vpad / 16) * h->S_d * 64 / wdiv);
+  const WMat head = dd_weight(h, 0, DD_M_LM_HEAD);
+  DA(h->lm_head, dd_weight_units(h, head));
+  if ((size_t)head.n_tiles * head.S > mx) mx = (size_t)head.n_tiles * head.S;
   if (h->wq) {
-    DA(h->s_lm, (size_t)h->Vpad * (h->wq == DD_WQ_MXFP4 ? h->S_d / 4 : 1));
-    size_t mx = (size_t)h->qkv_tiles * h->S_d;
-    if ((size_t)(2 * dff / 16) * h->S_d > mx) mx = (size_t)(2 * dff / 16) * h->S_d;
-    if ((size_t)(d / 16) * h->S_ff > mx) mx = (size_t)(d / 16) * h->S_ff;
-    if ((size_t)(h->Vpad / 16) * h->S_d > mx) mx = (size_t)(h->Vpad / 16) * h->S_d;
+    DA(h->s_lm, dd_weight_scales(h, head));
     DA(h->deq_tmp, mx * 64);
   }
   DA(h->final_norm, d);
@@ -297,27 +290,45 @@ extern "C" int dd_lm_create_shared(const dd_lm_config* c, dd_lm* weights_from, d
 // -----------------------------------------------------------------------------------------------
 // weights
 // -----------------------------------------------------------------------------------------------
+// Where a tensor of the checkpoint goes — the ONE table the three loaders share: its matrix (DD_M_*; -1: the embedding or a norm
+// vector), the first destination tile and the tile stride inside that matrix (q | k | v share one, gate and up tiles interleave), the
+// pack mode, the number of source tiles and the expected rows x cols.
+struct TensorDest {
+  int which, tile0, stride, mode, n_tiles, rows, cols;
+};
+static TensorDest tensor_dest(const dd_lm* h, int id) {
+  const int d = h->d, dff = h->dff;
+  switch (id) {
+    case DD_T_WQ: return {DD_M_QKV, 0, 1, PACK_ROPE, h->q_tiles, h->q_dim, d};
+    case DD_T_WK: return {DD_M_QKV, h->q_tiles, 1, PACK_ROPE, h->k_tiles, h->kv_dim, d};
+    case DD_T_WV: return {DD_M_QKV, h->q_tiles + h->k_tiles, 1, PACK_PLAIN, h->k_tiles, h->kv_dim, d};
+    case DD_T_WO: return {DD_M_O, 0, 1, PACK_PLAIN, d / 16, d, h->q_dim};
+    case DD_T_WGATE: return {DD_M_GATE_UP, 0, 2, PACK_PLAIN, dff / 16, dff, d};
+    case DD_T_WUP: return {DD_M_GATE_UP, 1, 2, PACK_PLAIN, dff / 16, dff, d};
+    case DD_T_WDOWN: return {DD_M_DOWN, 0, 1, PACK_PLAIN, d / 16, d, dff};
+    case DD_T_LM_HEAD: return {DD_M_LM_HEAD, 0, 1, PACK_PLAIN, h->Vpad / 16, h->V, d};
+    case DD_T_EMBED: return {-1, 0, 0, 0, 0, h->V, d};
+    default: return {-1, 0, 0, 0, 0, 1, d};   // DD_T_ATTN_NORM, DD_T_MLP_NORM, DD_T_FINAL_NORM
+  }
+}
+// the argument checks of the two quantised loaders (`who`: the exported name, for the error text)
+static int quantised_dest(const dd_lm* h, const char* who, int id, int layer, TensorDest* t) {
+  DD_REQUIRE(id == DD_T_LM_HEAD || (id >= DD_T_WQ && id <= DD_T_WDOWN && id != DD_T_MLP_NORM), "%s: tensor id %d is not a matrix", who, id);
+  DD_REQUIRE(id == DD_T_LM_HEAD || (layer >= 0 && layer < h->Lyr), "%s: layer %d out of range", who, layer);
+  *t = tensor_dest(h, id);
+  return DD_OK;
+}
+
 extern "C" int dd_lm_load_tensor(dd_lm* h, int id, int layer, const uint16_t* src, int rows, int cols, int on_device) {
   DD_REQUIRE(h && src, "dd_lm_load_tensor: null argument");
   DD_REQUIRE(!h->wsrc, "dd_lm_load_tensor: this handle borrows its weights (dd_lm_create_shared); load into the owner");
   DD_REQUIRE(id >= DD_T_EMBED && id <= DD_T_LM_HEAD, "dd_lm_load_tensor: unknown tensor id %d", id);
   bool per_layer = !(id == DD_T_EMBED || id == DD_T_FINAL_NORM || id == DD_T_LM_HEAD);
   DD_REQUIRE(!per_layer || (layer >= 0 && layer < h->Lyr), "dd_lm_load_tensor: layer %d out of range", layer);
-  const int d = h->d, dff = h->dff;
-  int er = 0, ec = 0;  // expected shape
-  switch (id) {
-    case DD_T_EMBED: er = h->V, ec = d; break;
-    case DD_T_LM_HEAD: er = h->V, ec = d; break;
-    case DD_T_ATTN_NORM: case DD_T_MLP_NORM: case DD_T_FINAL_NORM: er = 1, ec = d; break;
-    case DD_T_WQ: er = h->q_dim, ec = d; break;
-    case DD_T_WK: case DD_T_WV: er = h->kv_dim, ec = d; break;
-    case DD_T_WO: er = d, ec = h->q_dim; break;
-    case DD_T_WGATE: case DD_T_WUP: er = dff, ec = d; break;
-    case DD_T_WDOWN: er = d, ec = dff; break;
-  }
-  DD_REQUIRE((size_t)rows * cols == (size_t)er * ec && (er == 1 || (rows == er && cols == ec)),
-             "dd_lm_load_tensor: tensor %d expects %d x %d, got %d x %d", id, er, ec, rows, cols);
-  DD_REQUIRE(!h->wq || id == DD_T_EMBED || id == DD_T_ATTN_NORM || id == DD_T_MLP_NORM || id == DD_T_FINAL_NORM,
+  const TensorDest t = tensor_dest(h, id);
+  DD_REQUIRE((size_t)rows * cols == (size_t)t.rows * t.cols && (t.rows == 1 || (rows == t.rows && cols == t.cols)),
+             "dd_lm_load_tensor: tensor %d expects %d x %d, got %d x %d", id, t.rows, t.cols, rows, cols);
+  DD_REQUIRE(!h->wq || t.which < 0,
              "dd_lm_load_tensor: this engine stores fp8 / MXFP4 weights; load matrices with dd_lm_load_tensor_fp8 / dd_lm_load_tensor_mxfp4");
   size_t n = (size_t)rows * cols;
   const uint16_t* dev = src;
@@ -333,20 +344,13 @@ extern "C" int dd_lm_load_tensor(dd_lm* h, int id, int layer, const uint16_t* sr
     dev = staging;
   }
   int rc = DD_OK;
-  LayerW* w = per_layer ? &h->lw[layer] : nullptr;
-  switch (id) {
-    case DD_T_EMBED: rc = hipMemcpy(h->embed, dev, n * 2, hipMemcpyDeviceToDevice) == hipSuccess ? DD_OK : DD_EHIP; break;
-    case DD_T_ATTN_NORM: rc = ddk_bf16_to_f32(dev, w->norm1, d, nullptr, h->wf); break;
-    case DD_T_MLP_NORM: rc = ddk_bf16_to_f32(dev, w->norm2, d, nullptr, h->wf); break;
-    case DD_T_FINAL_NORM: rc = ddk_bf16_to_f32(dev, h->final_norm, d, nullptr, h->wf); break;
-    case DD_T_WQ: rc = ddk_pack_weight(dev, rows, cols, w->wqkv, 0, 1, PACK_ROPE, h->q_tiles, nullptr); break;
-    case DD_T_WK: rc = ddk_pack_weight(dev, rows, cols, w->wqkv, h->q_tiles, 1, PACK_ROPE, h->k_tiles, nullptr); break;
-    case DD_T_WV: rc = ddk_pack_weight(dev, rows, cols, w->wqkv, h->q_tiles + h->k_tiles, 1, PACK_PLAIN, h->k_tiles, nullptr); break;
-    case DD_T_WO: rc = ddk_pack_weight(dev, rows, cols, w->wo, 0, 1, PACK_PLAIN, d / 16, nullptr); break;
-    case DD_T_WGATE: rc = ddk_pack_weight(dev, rows, cols, w->wgu, 0, 2, PACK_PLAIN, dff / 16, nullptr); break;
-    case DD_T_WUP: rc = ddk_pack_weight(dev, rows, cols, w->wgu, 1, 2, PACK_PLAIN, dff / 16, nullptr); break;
-    case DD_T_WDOWN: rc = ddk_pack_weight(dev, rows, cols, w->wdown, 0, 1, PACK_PLAIN, d / 16, nullptr); break;
-    case DD_T_LM_HEAD: rc = ddk_pack_weight(dev, rows, cols, h->lm_head, 0, 1, PACK_PLAIN, h->Vpad / 16, nullptr); break;
+  if (t.which >= 0) {
+    rc = ddk_pack_weight(dev, rows, cols, dd_weight(h, layer, t.which).W, t.tile0, t.stride, t.mode, t.n_tiles, nullptr);
+  } else if (id == DD_T_EMBED) {
+    rc = hipMemcpy(h->embed, dev, n * 2, hipMemcpyDeviceToDevice) == hipSuccess ? DD_OK : DD_EHIP;
+  } else {
+    float* norm = id == DD_T_FINAL_NORM ? h->final_norm : (id == DD_T_ATTN_NORM ? h->lw[layer].norm1 : h->lw[layer].norm2);
+    rc = ddk_bf16_to_f32(dev, norm, h->d, nullptr, h->wf);
   }
   hipError_t e = hipDeviceSynchronize();
   if (staging) (void)hipFree(staging);
@@ -360,47 +364,29 @@ extern "C" int dd_lm_load_tensor_fp8(dd_lm* h, int id, int layer, const uint8_t*
   DD_REQUIRE(h && q && row_scale, "dd_lm_load_tensor_fp8: null argument");
   DD_REQUIRE(!h->wsrc, "dd_lm_load_tensor_fp8: this handle borrows its weights (dd_lm_create_shared); load into the owner");
   DD_REQUIRE(h->wq == DD_WQ_FP8, "dd_lm_load_tensor_fp8: the engine was not created for fp8 weights (weight_format 1)");
-  bool per_layer = id != DD_T_LM_HEAD;
-  DD_REQUIRE(id == DD_T_LM_HEAD || (id >= DD_T_WQ && id <= DD_T_WDOWN && id != DD_T_MLP_NORM),
-             "dd_lm_load_tensor_fp8: tensor id %d is not a matrix", id);
-  DD_REQUIRE(!per_layer || (layer >= 0 && layer < h->Lyr), "dd_lm_load_tensor_fp8: layer %d out of range", layer);
-  const int d = h->d, dff = h->dff;
-  int er = 0, ec = 0;
-  switch (id) {
-    case DD_T_LM_HEAD: er = h->V, ec = d; break;
-    case DD_T_WQ: er = h->q_dim, ec = d; break;
-    case DD_T_WK: case DD_T_WV: er = h->kv_dim, ec = d; break;
-    case DD_T_WO: er = d, ec = h->q_dim; break;
-    case DD_T_WGATE: case DD_T_WUP: er = dff, ec = d; break;
-    case DD_T_WDOWN: er = d, ec = dff; break;
-  }
-  DD_REQUIRE(rows == er && cols == ec, "dd_lm_load_tensor_fp8: tensor %d expects %d x %d, got %d x %d", id, er, ec, rows, cols);
+  TensorDest t;
+  RC(quantised_dest(h, "dd_lm_load_tensor_fp8", id, layer, &t));
+  DD_REQUIRE(rows == t.rows && cols == t.cols, "dd_lm_load_tensor_fp8: tensor %d expects %d x %d, got %d x %d", id, t.rows, t.cols, rows, cols);
+  // staging: [elements | row scales] in one allocation, freed on every path
+  const size_t nq = (size_t)rows * cols, off_s = (nq + 15) / 16 * 16;
+  uint8_t* stg = nullptr;
   const uint8_t* dq = q;
   const float* ds = row_scale;
-  uint8_t* sq = nullptr;
-  float* ss = nullptr;
   if (!on_device) {
-    DD_HIP(hipMalloc((void**)&sq, (size_t)rows * cols));
-    DD_HIP(hipMalloc((void**)&ss, (size_t)rows * 4));
-    DD_HIP(hipMemcpy(sq, q, (size_t)rows * cols, hipMemcpyHostToDevice));
-    DD_HIP(hipMemcpy(ss, row_scale, (size_t)rows * 4, hipMemcpyHostToDevice));
-    dq = sq, ds = ss;
+    DD_HIP(hipMalloc((void**)&stg, off_s + (size_t)rows * 4));
+    hipError_t e = hipMemcpy(stg, q, nq, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(stg + off_s, row_scale, (size_t)rows * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(stg);
+      dd_set_error("dd_lm_load_tensor_fp8: staging copy failed: %s", hipGetErrorString(e));
+      return DD_EHIP;
+    }
+    dq = stg, ds = (const float*)(stg + off_s);
   }
-  LayerW* w = per_layer ? &h->lw[layer] : nullptr;
-  int rc = DD_OK;
-  switch (id) {
-    case DD_T_WQ: rc = ddk_pack_weight_fp8(dq, ds, rows, cols, w->wqkv, w->s_qkv, 0, 1, PACK_ROPE, h->q_tiles, nullptr); break;
-    case DD_T_WK: rc = ddk_pack_weight_fp8(dq, ds, rows, cols, w->wqkv, w->s_qkv, h->q_tiles, 1, PACK_ROPE, h->k_tiles, nullptr); break;
-    case DD_T_WV: rc = ddk_pack_weight_fp8(dq, ds, rows, cols, w->wqkv, w->s_qkv, h->q_tiles + h->k_tiles, 1, PACK_PLAIN, h->k_tiles, nullptr); break;
-    case DD_T_WO: rc = ddk_pack_weight_fp8(dq, ds, rows, cols, w->wo, w->s_o, 0, 1, PACK_PLAIN, d / 16, nullptr); break;
-    case DD_T_WGATE: rc = ddk_pack_weight_fp8(dq, ds, rows, cols, w->wgu, w->s_gu, 0, 2, PACK_PLAIN, dff / 16, nullptr); break;
-    case DD_T_WUP: rc = ddk_pack_weight_fp8(dq, ds, rows, cols, w->wgu, w->s_gu, 1, 2, PACK_PLAIN, dff / 16, nullptr); break;
-    case DD_T_WDOWN: rc = ddk_pack_weight_fp8(dq, ds, rows, cols, w->wdown, w->s_down, 0, 1, PACK_PLAIN, d / 16, nullptr); break;
-    case DD_T_LM_HEAD: rc = ddk_pack_weight_fp8(dq, ds, rows, cols, h->lm_head, h->s_lm, 0, 1, PACK_PLAIN, h->Vpad / 16, nullptr); break;
-  }
+  const WMat m = dd_weight(h, layer, t.which);
+  int rc = ddk_pack_weight_fp8(dq, ds, rows, cols, m.W, m.scale, t.tile0, t.stride, t.mode, t.n_tiles, nullptr);
   hipError_t e = hipDeviceSynchronize();
-  if (sq) (void)hipFree(sq);
-  if (ss) (void)hipFree(ss);
+  if (stg) (void)hipFree(stg);
   if (rc != DD_OK) return rc;
   DD_HIP(e);
   return DD_OK;
@@ -411,21 +397,9 @@ extern "C" int dd_lm_load_tensor_mxfp4(dd_lm* h, int id, int layer, const uint8_
   DD_REQUIRE(h && q && scale, "dd_lm_load_tensor_mxfp4: null argument");
   DD_REQUIRE(!h->wsrc, "dd_lm_load_tensor_mxfp4: this handle borrows its weights (dd_lm_create_shared); load into the owner");
   DD_REQUIRE(h->wq == DD_WQ_MXFP4, "dd_lm_load_tensor_mxfp4: the engine was not created for MXFP4 weights (weight_format 3)");
-  bool per_layer = id != DD_T_LM_HEAD;
-  DD_REQUIRE(id == DD_T_LM_HEAD || (id >= DD_T_WQ && id <= DD_T_WDOWN && id != DD_T_MLP_NORM),
-             "dd_lm_load_tensor_mxfp4: tensor id %d is not a matrix", id);
-  DD_REQUIRE(!per_layer || (layer >= 0 && layer < h->Lyr), "dd_lm_load_tensor_mxfp4: layer %d out of range", layer);
-  const int d = h->d, dff = h->dff;
-  int er = 0, ec = 0;
-  switch (id) {
-    case DD_T_LM_HEAD: er = h->V, ec = d; break;
-    case DD_T_WQ: er = h->q_dim, ec = d; break;
-    case DD_T_WK: case DD_T_WV: er = h->kv_dim, ec = d; break;
-    case DD_T_WO: er = d, ec = h->q_dim; break;
-    case DD_T_WGATE: case DD_T_WUP: er = dff, ec = d; break;
-    case DD_T_WDOWN: er = d, ec = dff; break;
-  }
-  DD_REQUIRE(rows == er && cols == ec, "dd_lm_load_tensor_mxfp4: tensor %d expects %d x %d, got %d x %d", id, er, ec, rows, cols);
+  TensorDest t;
+  RC(quantised_dest(h, "dd_lm_load_tensor_mxfp4", id, layer, &t));
+  DD_REQUIRE(rows == t.rows && cols == t.cols, "dd_lm_load_tensor_mxfp4: tensor %d expects %d x %d, got %d x %d", id, t.rows, t.cols, rows, cols);
   const size_t nq = (size_t)rows * (cols / 2), ns = (size_t)rows * (cols / 32);
   // staging: [elements | scales | flag] in one allocation (the flag: a scale byte outside [7, 247] met while packing)
   const size_t off_s = on_device ? 0 : (nq + 15) / 16 * 16, off_f = on_device ? 0 : off_s + (ns + 15) / 16 * 16;
@@ -444,19 +418,8 @@ extern "C" int dd_lm_load_tensor_mxfp4(dd_lm* h, int id, int layer, const uint8_
     return DD_EHIP;
   }
   int32_t* bad = (int32_t*)(stg + off_f);
-  LayerW* w = per_layer ? &h->lw[layer] : nullptr;
-  auto sw = [](float* p) { return (uint32_t*)p; };
-  int rc = DD_OK;
-  switch (id) {
-    case DD_T_WQ: rc = ddk_pack_weight_mxfp4(dq, ds, rows, cols, w->wqkv, sw(w->s_qkv), 0, 1, PACK_ROPE, h->q_tiles, bad, nullptr); break;
-    case DD_T_WK: rc = ddk_pack_weight_mxfp4(dq, ds, rows, cols, w->wqkv, sw(w->s_qkv), h->q_tiles, 1, PACK_ROPE, h->k_tiles, bad, nullptr); break;
-    case DD_T_WV: rc = ddk_pack_weight_mxfp4(dq, ds, rows, cols, w->wqkv, sw(w->s_qkv), h->q_tiles + h->k_tiles, 1, PACK_PLAIN, h->k_tiles, bad, nullptr); break;
-    case DD_T_WO: rc = ddk_pack_weight_mxfp4(dq, ds, rows, cols, w->wo, sw(w->s_o), 0, 1, PACK_PLAIN, d / 16, bad, nullptr); break;
-    case DD_T_WGATE: rc = ddk_pack_weight_mxfp4(dq, ds, rows, cols, w->wgu, sw(w->s_gu), 0, 2, PACK_PLAIN, dff / 16, bad, nullptr); break;
-    case DD_T_WUP: rc = ddk_pack_weight_mxfp4(dq, ds, rows, cols, w->wgu, sw(w->s_gu), 1, 2, PACK_PLAIN, dff / 16, bad, nullptr); break;
-    case DD_T_WDOWN: rc = ddk_pack_weight_mxfp4(dq, ds, rows, cols, w->wdown, sw(w->s_down), 0, 1, PACK_PLAIN, d / 16, bad, nullptr); break;
-    case DD_T_LM_HEAD: rc = ddk_pack_weight_mxfp4(dq, ds, rows, cols, h->lm_head, sw(h->s_lm), 0, 1, PACK_PLAIN, h->Vpad / 16, bad, nullptr); break;
-  }
+  const WMat m = dd_weight(h, layer, t.which);
+  int rc = ddk_pack_weight_mxfp4(dq, ds, rows, cols, m.W, (uint32_t*)m.scale, t.tile0, t.stride, t.mode, t.n_tiles, bad, nullptr);
   int32_t bad_host = 0;
   e = hipDeviceSynchronize();
   if (e == hipSuccess && rc == DD_OK) e = hipMemcpy(&bad_host, bad, 4, hipMemcpyDeviceToHost);
@@ -467,71 +430,40 @@ extern "C" int dd_lm_load_tensor_mxfp4(dd_lm* h, int id, int layer, const uint8_
   return DD_OK;
 }
 
+// Synthetic weights.  Per storage kind one seed sequence (a fresh seed per matrix in table order, then lm_head, the embedding last):
+//   16-bit  normal(0, std) in the engine's 16-bit type
+//   fp8     random finite e4m3 bytes (|q| <= 240, rms ~ 40) with a constant row scale that gives ~std
+//   MXFP4   random e2m1 codes (rms 2.93) with one constant block scale: the power of two nearest std / 2.93
 extern "C" int dd_lm_load_synthetic(dd_lm* h, uint32_t seed, float std) {
   DD_REQUIRE(h && !h->wsrc, "dd_lm_load_synthetic: null handle, or a handle that borrows its weights");
-  DD_REQUIRE(h, "dd_lm_load_synthetic: null handle");
-  const int d = h->d, dff = h->dff;
-  if (h->wq == DD_WQ_MXFP4) {   // random e2m1 codes (rms 2.93) with one constant block scale: the power of two nearest std / 2.93
-    uint32_t s4 = seed * 2654435761u + 13;
-    int e = (int)lrintf(log2f((std > 0.f ? std : 1e-30f) / 2.926f));
-    e = e < -120 ? -120 : (e > 120 ? 120 : e);
-    const uint32_t sb = (uint32_t)(e + 127) * 0x01010101u;
-    for (int l = 0; l < h->Lyr; ++l) {
-      LayerW& w = h->lw[l];
-      RC(ddk_fill_synthetic_mxfp4((uint8_t*)w.wqkv, (size_t)h->qkv_tiles * h->S_d * 256, s4++, nullptr));
-      RC(ddk_fill_synthetic_mxfp4((uint8_t*)w.wo, (size_t)(d / 16) * h->S_q * 256, s4++, nullptr));
-      RC(ddk_fill_synthetic_mxfp4((uint8_t*)w.wgu, (size_t)(2 * dff / 16) * h->S_d * 256, s4++, nullptr));
-      RC(ddk_fill_synthetic_mxfp4((uint8_t*)w.wdown, (size_t)(d / 16) * h->S_ff * 256, s4++, nullptr));
-      RC(ddk_fill_const_u32((uint32_t*)w.s_qkv, (size_t)h->qkv_tiles * 4 * h->S_d, sb, nullptr));
-      RC(ddk_fill_const_u32((uint32_t*)w.s_o, (size_t)(d / 16) * 4 * h->S_q, sb, nullptr));
-      RC(ddk_fill_const_u32((uint32_t*)w.s_gu, (size_t)(2 * dff / 16) * 4 * h->S_d, sb, nullptr));
-      RC(ddk_fill_const_u32((uint32_t*)w.s_down, (size_t)(d / 16) * 4 * h->S_ff, sb, nullptr));
-      RC(ddk_fill_const_f32(w.norm1, d, 1.0f, nullptr));
-      RC(ddk_fill_const_f32(w.norm2, d, 1.0f, nullptr));
-    }
-    RC(ddk_fill_synthetic_mxfp4((uint8_t*)h->lm_head, (size_t)(h->Vpad / 16) * h->S_d * 256, s4++, nullptr));
-    RC(ddk_fill_const_u32((uint32_t*)h->s_lm, (size_t)(h->Vpad / 16) * 4 * h->S_d, sb, nullptr));
-    RC(ddk_fill_const_f32(h->final_norm, d, 1.0f, nullptr));
-    RC(ddk_fill_synthetic(h->embed, (size_t)h->V * d, s4++, 1.0f, nullptr));
-    DD_HIP(hipDeviceSynchronize());
-    return DD_OK;
-  }
-  if (h->wq) {   // random finite e4m3 bytes (|q| <= 240, rms ~ 40) with a constant row scale that gives ~std
-    uint32_t s8 = seed * 2654435761u + 7;
-    const float sc = std / 40.0f;
-    for (int l = 0; l < h->Lyr; ++l) {
-      LayerW& w = h->lw[l];
-      RC(ddk_fill_synthetic_fp8((uint8_t*)w.wqkv, (size_t)h->qkv_tiles * h->S_d * 512, s8++, nullptr));
-      RC(ddk_fill_synthetic_fp8((uint8_t*)w.wo, (size_t)(d / 16) * h->S_q * 512, s8++, nullptr));
-      RC(ddk_fill_synthetic_fp8((uint8_t*)w.wgu, (size_t)(2 * dff / 16) * h->S_d * 512, s8++, nullptr));
-      RC(ddk_fill_synthetic_fp8((uint8_t*)w.wdown, (size_t)(d / 16) * h->S_ff * 512, s8++, nullptr));
-      RC(ddk_fill_const_f32(w.s_qkv, (size_t)h->qkv_tiles * 16, sc, nullptr));
-      RC(ddk_fill_const_f32(w.s_o, d, sc, nullptr));
-      RC(ddk_fill_const_f32(w.s_gu, (size_t)2 * dff, sc, nullptr));
-      RC(ddk_fill_const_f32(w.s_down, d, sc, nullptr));
-      RC(ddk_fill_const_f32(w.norm1, d, 1.0f, nullptr));
-      RC(ddk_fill_const_f32(w.norm2, d, 1.0f, nullptr));
-    }
-    RC(ddk_fill_synthetic_fp8((uint8_t*)h->lm_head, (size_t)(h->Vpad / 16) * h->S_d * 512, s8++, nullptr));
-    RC(ddk_fill_const_f32(h->s_lm, h->Vpad, sc, nullptr));
-    RC(ddk_fill_const_f32(h->final_norm, d, 1.0f, nullptr));
-    RC(ddk_fill_synthetic(h->embed, (size_t)h->V * d, s8++, 1.0f, nullptr));
-    DD_HIP(hipDeviceSynchronize());
-    return DD_OK;
-  }
-  uint32_t s = seed * 2654435761u + 1;
+  const int d = h->d;
+  const bool mx = h->wq == DD_WQ_MXFP4;
+  uint32_t s = seed * 2654435761u + (mx ? 13 : (h->wq ? 7 : 1));
+  int e = (int)lrintf(log2f((std > 0.f ? std : 1e-30f) / 2.926f));
+  e = e < -120 ? -120 : (e > 120 ? 120 : e);
+  const uint32_t sb = (uint32_t)(e + 127) * 0x01010101u;
+  const float sc = std / 40.0f;
+  auto fill = [&](const WMat& m) -> int {
+    const size_t bytes = dd_weight_units(h, m) * sizeof(u32x4_t);
+    if (mx) return ddk_fill_synthetic_mxfp4((uint8_t*)m.W, bytes, s++, nullptr);
+    if (h->wq) return ddk_fill_synthetic_fp8((uint8_t*)m.W, bytes, s++, nullptr);
+    return ddk_fill_synthetic((uint16_t*)m.W, bytes / 2, s++, std, nullptr, h->wf);
+  };
+  auto fill_scale = [&](const WMat& m) -> int {
+    if (mx) return ddk_fill_const_u32((uint32_t*)m.scale, dd_weight_scales(h, m), sb, nullptr);
+    return ddk_fill_const_f32(m.scale, dd_weight_scales(h, m), sc, nullptr);
+  };
   for (int l = 0; l < h->Lyr; ++l) {
-    LayerW& w = h->lw[l];
-    RC(ddk_fill_synthetic((uint16_t*)w.wqkv, (size_t)h->qkv_tiles * h->S_d * 512, s++, std, nullptr, h->wf));
-    RC(ddk_fill_synthetic((uint16_t*)w.wo, (size_t)(d / 16) * h->S_q * 512, s++, std, nullptr, h->wf));
-    RC(ddk_fill_synthetic((uint16_t*)w.wgu, (size_t)(2 * dff / 16) * h->S_d * 512, s++, std, nullptr, h->wf));
-    RC(ddk_fill_synthetic((uint16_t*)w.wdown, (size_t)(d / 16) * h->S_ff * 512, s++, std, nullptr, h->wf));
-    RC(ddk_fill_const_f32(w.norm1, d, 1.0f, nullptr));
-    RC(ddk_fill_const_f32(w.norm2, d, 1.0f, nullptr));
+    for (int k = DD_M_QKV; k <= DD_M_DOWN; ++k) RC(fill(dd_weight(h, l, k)));
+    for (int k = DD_M_QKV; k <= DD_M_DOWN && h->wq; ++k) RC(fill_scale(dd_weight(h, l, k)));
+    RC(ddk_fill_const_f32(h->lw[l].norm1, d, 1.0f, nullptr));
+    RC(ddk_fill_const_f32(h->lw[l].norm2, d, 1.0f, nullptr));
   }
-  RC(ddk_fill_synthetic((uint16_t*)h->lm_head, (size_t)(h->Vpad / 16) * h->S_d * 512, s++, std, nullptr, h->wf));
+  const WMat head = dd_weight(h, 0, DD_M_LM_HEAD);
+  RC(fill(head));
+  if (h->wq) RC(fill_scale(head));
   RC(ddk_fill_const_f32(h->final_norm, d, 1.0f, nullptr));
-  RC(ddk_fill_synthetic(h->embed, (size_t)h->V * d, s++, 1.0f, nullptr, h->wf));
+  RC(ddk_fill_synthetic(h->embed, (size_t)h->V * d, s++, 1.0f, nullptr, h->wf));   // (fp8 / MXFP4 engines: wf == 0)
   DD_HIP(hipDeviceSynchronize());
   return DD_OK;
 }
@@ -713,48 +645,28 @@ __global__ __launch_bounds__(1024) void k_first_token_from_member(DDState* st, c
 // the member's zero columns of the 2-D attention mask (first-token ensemble), or nullptr for the un-masked pass.
 static int prefill_layers(dd_lm* h, int T0, const uint8_t* drop_plane, int drop_bit, int span_start, int span_len,
                           hipStream_t st, int pos0 = 0) {
-  const int d = h->d, dff = h->dff;
-  // fp8 storage: the prefill GEMM runs on a bf16 expansion of ONE matrix at a time (exact), scales in its epilogue
-  auto wsel = [&](GemmArgs& g, u32x4_t* W, float* scale, int n_tiles, int S) -> int {
-    if (!h->wq) {
-      g.W = W;
-      return DD_OK;
-    }
-    g.W = h->deq_tmp;
-    if (h->wq == DD_WQ_MXFP4) return ddk_dequant_tiles_mxfp4(W, (const uint32_t*)scale, h->deq_tmp, n_tiles, S, st);   // block scales applied: no wscale
-    g.wscale = scale;
-    return ddk_dequant_tiles(W, h->deq_tmp, n_tiles, S, st);
-  };
+  const int d = h->d;
   for (int l = 0; l < h->Lyr; ++l) {
     LayerW& w = h->lw[l];
     RC(ddk_rmsnorm_split(h->px, T0, d, w.norm1, h->cfg.rms_eps, h->p1_hi, h->p1_lo, nullptr, nullptr, st, h->wf));
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.wf = h->wf;
-    g.a_hi = h->p1_hi, g.a_lo = h->p1_lo, g.M = T0, g.S = h->S_d, g.n_tiles = h->qkv_tiles;
-    RC(wsel(g, w.wqkv, w.s_qkv, h->qkv_tiles, h->S_d));
-    g.qbuf = h->pq, g.kc = h->kc + (size_t)l * h->lsk, g.vc = h->vc + (size_t)l * h->lsv, g.T_cap = h->T_cap;
-    g.q_tiles = h->q_tiles, g.k_tiles = h->k_tiles, g.q_dim = h->q_dim, g.kv_dim = h->kv_dim, g.pos0 = pos0, g.kv16 = h->kv16;
-    g.rope_cos = h->rope_cos, g.rope_sin = h->rope_sin;
+    GemmArgs g = dd_gemm_qkv(h, l, h->p1_hi, h->p1_lo, T0);
+    RC(dd_gemm_weight(h, l, DD_M_QKV, g, st));
+    g.qbuf = h->pq, g.kc = h->kc + (size_t)l * h->lsk, g.vc = h->vc + (size_t)l * h->lsv, g.pos0 = pos0;
     RC(ddk_gemm(EPI_QKV, g, st));
     RC(ddk_attn_prefill(h->pq, g.kc, g.vc, T0, h->T_cap, h->H, h->Hkv, h->p1_hi, h->p1_lo, drop_plane, drop_bit,
                         span_start, span_len, pos0, st, nullptr, h->kv16, h->wf));
-    memset(&g, 0, sizeof(g));
-    g.wf = h->wf;
-    g.a_hi = h->p1_hi, g.a_lo = h->p1_lo, g.M = T0, g.S = h->S_q, g.n_tiles = d / 16, g.out = h->px, g.ldo = d;
-    RC(wsel(g, w.wo, w.s_o, d / 16, h->S_q));
+    g = dd_gemm_o(h, l, h->p1_hi, h->p1_lo, T0);
+    RC(dd_gemm_weight(h, l, DD_M_O, g, st));
+    g.out = h->px;
     RC(ddk_gemm(EPI_RESID, g, st));
     RC(ddk_rmsnorm_split(h->px, T0, d, w.norm2, h->cfg.rms_eps, h->p1_hi, h->p1_lo, nullptr, nullptr, st, h->wf));
-    memset(&g, 0, sizeof(g));
-    g.wf = h->wf;
-    g.a_hi = h->p1_hi, g.a_lo = h->p1_lo, g.M = T0, g.S = h->S_d, g.n_tiles = 2 * dff / 16;
-    RC(wsel(g, w.wgu, w.s_gu, 2 * dff / 16, h->S_d));
-    g.o_hi = h->p2_hi, g.o_lo = h->p2_lo, g.ld_planes = dff;
+    g = dd_gemm_gate_up(h, l, h->p1_hi, h->p1_lo, T0);
+    RC(dd_gemm_weight(h, l, DD_M_GATE_UP, g, st));
+    g.o_hi = h->p2_hi, g.o_lo = h->p2_lo;
     RC(ddk_gemm(EPI_SILU, g, st));
-    memset(&g, 0, sizeof(g));
-    g.wf = h->wf;
-    g.a_hi = h->p2_hi, g.a_lo = h->p2_lo, g.M = T0, g.S = h->S_ff, g.n_tiles = d / 16, g.out = h->px, g.ldo = d;
-    RC(wsel(g, w.wdown, w.s_down, d / 16, h->S_ff));
+    g = dd_gemm_down(h, l, h->p2_hi, h->p2_lo, T0);
+    RC(dd_gemm_weight(h, l, DD_M_DOWN, g, st));
+    g.out = h->px;
     RC(ddk_gemm(EPI_RESID, g, st));
   }
   return DD_OK;
@@ -771,20 +683,9 @@ static int prefill_head(dd_lm* h, const int32_t* row_index, int n_rows, float* l
                         const float* src = nullptr, float* rowstat = nullptr, int rowstat_ld = 0) {
   const int d = h->d;
   RC(ddk_rmsnorm_split(src ? src : h->px, n_rows, d, h->final_norm, h->cfg.rms_eps, h->p1_hi, h->p1_lo, row_index, h->pq, st, h->wf));
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.wf = h->wf;
-  g.a_hi = h->p1_hi, g.a_lo = h->p1_lo, g.M = n_rows, g.S = h->S_d, g.n_tiles = h->Vpad / 16;
-  if (!h->wq) {
-    g.W = h->lm_head;
-  } else if (h->wq == DD_WQ_MXFP4) {
-    RC(ddk_dequant_tiles_mxfp4(h->lm_head, (const uint32_t*)h->s_lm, h->deq_tmp, h->Vpad / 16, h->S_d, st));
-    g.W = h->deq_tmp;
-  } else {
-    RC(ddk_dequant_tiles(h->lm_head, h->deq_tmp, h->Vpad / 16, h->S_d, st));
-    g.W = h->deq_tmp, g.wscale = h->s_lm;
-  }
-  g.out = logits, g.ldo = h->Vpad, g.n_valid = h->V;
+  GemmArgs g = dd_gemm_lm_head(h, h->p1_hi, h->p1_lo, n_rows);
+  RC(dd_gemm_weight(h, 0, DD_M_LM_HEAD, g, st));
+  g.out = logits;
   g.rowstat = rowstat, g.rowstat_ld = rowstat_ld;
   return ddk_gemm(EPI_STORE, g, st);
 }
@@ -923,26 +824,12 @@ extern "C" int dd_lm_prefill_group(dd_lm* const* lanes, int n, const float* cons
   DD_HIP(hipMemsetAsync(bx, 0, M * d * 4, st));            // padding rows: zeros (finite everywhere downstream, never stored)
   for (int i = 0; i < n; ++i)
     DD_HIP(hipMemcpyAsync(bx + (size_t)i * seq_rows * d, embeds[i], (size_t)T0s[i] * d * 4, hipMemcpyDeviceToDevice, st));
-  auto wsel = [&](GemmArgs& g, u32x4_t* W, float* scale, int n_tiles, int S) -> int {      // as in prefill_layers
-    if (!h0->wq) {
-      g.W = W;
-      return DD_OK;
-    }
-    g.W = h0->deq_tmp;
-    if (h0->wq == DD_WQ_MXFP4) return ddk_dequant_tiles_mxfp4(W, (const uint32_t*)scale, h0->deq_tmp, n_tiles, S, st);
-    g.wscale = scale;
-    return ddk_dequant_tiles(W, h0->deq_tmp, n_tiles, S, st);
-  };
   for (int l = 0; l < h0->Lyr; ++l) {
     LayerW& w = h0->lw[l];
     RC(ddk_rmsnorm_split(bx, (int)M, d, w.norm1, h0->cfg.rms_eps, b1h, b1l, nullptr, nullptr, st, h0->wf));
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.wf = h0->wf;
-    g.a_hi = b1h, g.a_lo = b1l, g.M = (int)M, g.S = h0->S_d, g.n_tiles = h0->qkv_tiles;
-    RC(wsel(g, w.wqkv, w.s_qkv, h0->qkv_tiles, h0->S_d));
-    g.qbuf = bq, g.T_cap = h0->T_cap, g.q_tiles = h0->q_tiles, g.k_tiles = h0->k_tiles, g.q_dim = h0->q_dim, g.kv_dim = h0->kv_dim;
-    g.pos0 = 0, g.kv16 = h0->kv16, g.rope_cos = h0->rope_cos, g.rope_sin = h0->rope_sin;
+    GemmArgs g = dd_gemm_qkv(h0, l, b1h, b1l, (int)M);
+    RC(dd_gemm_weight(h0, l, DD_M_QKV, g, st));
+    g.qbuf = bq;
     g.seq_rows = seq_rows, g.seq_tab = h0->seq_tab, g.seq_off_k = (size_t)l * h0->lsk, g.seq_off_v = (size_t)l * h0->lsv;
     g.kc = lanes[0]->kc + g.seq_off_k, g.vc = lanes[0]->vc + g.seq_off_v;
     RC(ddk_gemm(EPI_QKV, g, st));
@@ -956,22 +843,18 @@ extern "C" int dd_lm_prefill_group(dd_lm* const* lanes, int n, const float* cons
                             b1h + r0 * h0->q_dim, b1l + r0 * h0->q_dim, nullptr, 0, span_starts[i], span_lens[i], 0, st, nullptr, h0->kv16, h0->wf));
       }
     }
-    memset(&g, 0, sizeof(g));
-    g.wf = h0->wf;
-    g.a_hi = b1h, g.a_lo = b1l, g.M = (int)M, g.S = h0->S_q, g.n_tiles = d / 16, g.out = bx, g.ldo = d;
-    RC(wsel(g, w.wo, w.s_o, d / 16, h0->S_q));
+    g = dd_gemm_o(h0, l, b1h, b1l, (int)M);
+    RC(dd_gemm_weight(h0, l, DD_M_O, g, st));
+    g.out = bx;
     RC(ddk_gemm(EPI_RESID, g, st));
     RC(ddk_rmsnorm_split(bx, (int)M, d, w.norm2, h0->cfg.rms_eps, b1h, b1l, nullptr, nullptr, st, h0->wf));
-    memset(&g, 0, sizeof(g));
-    g.wf = h0->wf;
-    g.a_hi = b1h, g.a_lo = b1l, g.M = (int)M, g.S = h0->S_d, g.n_tiles = 2 * dff / 16;
-    RC(wsel(g, w.wgu, w.s_gu, 2 * dff / 16, h0->S_d));
-    g.o_hi = b2h, g.o_lo = b2l, g.ld_planes = dff;
+    g = dd_gemm_gate_up(h0, l, b1h, b1l, (int)M);
+    RC(dd_gemm_weight(h0, l, DD_M_GATE_UP, g, st));
+    g.o_hi = b2h, g.o_lo = b2l;
     RC(ddk_gemm(EPI_SILU, g, st));
-    memset(&g, 0, sizeof(g));
-    g.wf = h0->wf;
-    g.a_hi = b2h, g.a_lo = b2l, g.M = (int)M, g.S = h0->S_ff, g.n_tiles = d / 16, g.out = bx, g.ldo = d;
-    RC(wsel(g, w.wdown, w.s_down, d / 16, h0->S_ff));
+    g = dd_gemm_down(h0, l, b2h, b2l, (int)M);
+    RC(dd_gemm_weight(h0, l, DD_M_DOWN, g, st));
+    g.out = bx;
     RC(ddk_gemm(EPI_RESID, g, st));
   }
   for (int i = 0; i < n; ++i) RC(prefill_tail(lanes[i], bx + (size_t)i * seq_rows * d, T0s[i], span_starts[i], span_lens[i], st));
@@ -1007,7 +890,7 @@ static int g_extend_rows = 1;   // dd_set_tuning key 11: chunks of <= 32 rows th
 void dd_engine_set_extend_rows(int on) { g_extend_rows = on; }
 
 static int prefill_extend_rows(dd_lm* h, const float* embeds, int n, hipStream_t st) {
-  const int d = h->d, dff = h->dff, pos0 = h->T_host;
+  const int d = h->d, pos0 = h->T_host;
   const int cap = n <= 8 ? 8 : (n <= 16 ? 16 : 32), ng = cap / 8;
   auto gemv = [&](int epi, GemvArgs& a) -> int {
     a.nb = cap == 8 ? n : 8;
@@ -1020,16 +903,10 @@ static int prefill_extend_rows(dd_lm* h, const float* embeds, int n, hipStream_t
   RC(ddk_pack_embed_rows(embeds, n, cap, d, h->xa, h->lw[0].norm1, h->xop_d, h->ssq_a, d / 16, st, h->wf));
   int ssq_n = 1;
   for (int l = 0; l < h->Lyr; ++l) {
-    LayerW& w = h->lw[l];
     float* kc = h->kc + (size_t)l * h->lsk;
     float* vc = h->vc + (size_t)l * h->lsv;
-    GemvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.wf = h->wf;
-    a.W = w.wqkv, a.S = h->S_d, a.n_tiles = h->qkv_tiles, a.xop = h->xop_d, a.wq = h->wq, a.wscale = w.s_qkv;
-    a.ssq_in = h->ssq_a, a.ssq_n = ssq_n, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps;
-    a.qbuf = h->qbuf, a.knew = h->chunk_k, a.vnew = h->chunk_v, a.q_tiles = h->q_tiles, a.k_tiles = h->k_tiles;
-    a.q_dim = h->q_dim, a.kv_dim = h->kv_dim, a.rope_cos = h->rope_cos, a.rope_sin = h->rope_sin, a.state = h->chunk_states;
+    GemvArgs a = dd_gemv_qkv(h, l, ssq_n);
+    a.knew = h->chunk_k, a.vnew = h->chunk_v, a.state = h->chunk_states;
     for (int m = 0; m < cap; ++m) a.state_rows[m] = h->chunk_states + (m < n ? m : 0);
     RC(gemv(EPI_QKV, a));
     RC(ddk_scatter_kv_rows(h->chunk_k, h->chunk_v, n, h->kv_dim, kc, vc, h->T_cap, h->state, st, h->kv16));
@@ -1051,22 +928,11 @@ static int prefill_extend_rows(dd_lm* h, const float* embeds, int n, hipStream_t
       }
       RC(ddk_attn_decode(t, st));
     }
-    memset(&a, 0, sizeof(a));
-    a.wf = h->wf;
-    a.W = w.wo, a.S = h->S_q, a.n_tiles = d / 16, a.xop = h->xop_q, a.wq = h->wq, a.wscale = w.s_o;
-    a.out = h->xa, a.ldo = d, a.normw_next = w.norm2, a.xop_next = h->xop_d, a.S_next = h->S_d, a.ssq_out = h->ssq_b, a.ssq_ld = d / 16;
+    a = dd_gemv_o(h, l);
     RC(gemv(EPI_RESID, a));
-    memset(&a, 0, sizeof(a));
-    a.wf = h->wf;
-    a.W = w.wgu, a.S = h->S_d, a.n_tiles = dff / 16, a.xop = h->xop_d, a.wq = h->wq, a.wscale = w.s_gu;
-    a.ssq_in = h->ssq_b, a.ssq_n = d / 16, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps;
-    a.xop_next = h->xop_ff, a.S_next = h->S_ff;
+    a = dd_gemv_gate_up(h, l);
     RC(gemv(EPI_SILU, a));
-    memset(&a, 0, sizeof(a));
-    a.wf = h->wf;
-    a.W = w.wdown, a.S = h->S_ff, a.n_tiles = d / 16, a.xop = h->xop_ff, a.wq = h->wq, a.wscale = w.s_down;
-    a.out = h->xa, a.ldo = d, a.normw_next = (l + 1 < h->Lyr) ? h->lw[l + 1].norm1 : h->final_norm;
-    a.xop_next = h->xop_d, a.S_next = h->S_d, a.ssq_out = h->ssq_a, a.ssq_ld = d / 16;
+    a = dd_gemv_down(h, l);
     RC(gemv(EPI_RESID, a));
     ssq_n = d / 16;
   }
@@ -1189,7 +1055,7 @@ extern "C" int dd_lm_prefill_ensemble(dd_lm* h, const float* embeds, int T0, int
 // and leak bits; scratch, weights and the per-layer new K/V rows are this handle's (the first lane of the group).
 int lm_sweep(dd_lm* h, int nb, const uint8_t* bits, int row0, float* logits_out, hipStream_t st, dd_lm* const* lanes,
              const int32_t* skip_if) {
-  const int d = h->d, dff = h->dff;
+  const int d = h->d;
   // more than 8 lanes: the base rows fill two (up to 16 lanes), four (32) or eight (64) operand planes and go through the
   // grouped GEMV
   const bool wide = lanes && nb > 8;
@@ -1211,17 +1077,10 @@ int lm_sweep(dd_lm* h, int nb, const uint8_t* bits, int row0, float* logits_out,
   }
   int ssq_n = 1;
   for (int l = 0; l < h->Lyr; ++l) {
-    LayerW& w = h->lw[l];
     float* knew = h->knew + ((size_t)l * KV_ROWS + row0) * h->kv_dim;
     float* vnew = h->vnew + ((size_t)l * KV_ROWS + row0) * h->kv_dim;
-    GemvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.wf = h->wf;
-    a.W = w.wqkv, a.S = h->S_d, a.n_tiles = h->qkv_tiles, a.nb = nb, a.xop = h->xop_d;
-    a.wq = h->wq, a.wscale = w.s_qkv;
-    a.ssq_in = h->ssq_a, a.ssq_n = ssq_n, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps;
-    a.qbuf = h->qbuf, a.knew = knew, a.vnew = vnew, a.q_tiles = h->q_tiles, a.k_tiles = h->k_tiles;
-    a.q_dim = h->q_dim, a.kv_dim = h->kv_dim, a.rope_cos = h->rope_cos, a.rope_sin = h->rope_sin, a.state = h->state;
+    GemvArgs a = dd_gemv_qkv(h, l, ssq_n);
+    a.nb = nb, a.knew = knew, a.vnew = vnew, a.state = h->state;
     if (lanes)
       for (int m = 0; m < nb; ++m) a.state_rows[m] = lanes[m]->state;
     RC(gemv(EPI_QKV, a));
@@ -1253,34 +1112,19 @@ int lm_sweep(dd_lm* h, int nb, const uint8_t* bits, int row0, float* logits_out,
     } else {
       RC(ddk_attn_decode(t, st));
     }
-    memset(&a, 0, sizeof(a));
-    a.wf = h->wf;
-    a.W = w.wo, a.S = h->S_q, a.n_tiles = d / 16, a.nb = nb, a.xop = h->xop_q;
-    a.wq = h->wq, a.wscale = w.s_o;
-    a.out = h->xa, a.ldo = d, a.normw_next = w.norm2, a.xop_next = h->xop_d, a.S_next = h->S_d, a.ssq_out = h->ssq_b, a.ssq_ld = d / 16;
+    a = dd_gemv_o(h, l);
+    a.nb = nb;
     RC(gemv(EPI_RESID, a));
-    memset(&a, 0, sizeof(a));
-    a.wf = h->wf;
-    a.W = w.wgu, a.S = h->S_d, a.n_tiles = dff / 16, a.nb = nb, a.xop = h->xop_d;
-    a.wq = h->wq, a.wscale = w.s_gu;
-    a.ssq_in = h->ssq_b, a.ssq_n = d / 16, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps, a.xop_next = h->xop_ff, a.S_next = h->S_ff;
+    a = dd_gemv_gate_up(h, l);
+    a.nb = nb;
     RC(gemv(EPI_SILU, a));
-    memset(&a, 0, sizeof(a));
-    a.wf = h->wf;
-    a.W = w.wdown, a.S = h->S_ff, a.n_tiles = d / 16, a.nb = nb, a.xop = h->xop_ff;
-    a.wq = h->wq, a.wscale = w.s_down;
-    a.out = h->xa, a.ldo = d, a.normw_next = (l + 1 < h->Lyr) ? h->lw[l + 1].norm1 : h->final_norm;
-    a.xop_next = h->xop_d, a.S_next = h->S_d, a.ssq_out = h->ssq_a, a.ssq_ld = d / 16;
+    a = dd_gemv_down(h, l);
+    a.nb = nb;
     RC(gemv(EPI_RESID, a));
     ssq_n = d / 16;
   }
-  GemvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.wf = h->wf;
-  a.W = h->lm_head, a.S = h->S_d, a.n_tiles = h->Vpad / 16, a.nb = nb, a.xop = h->xop_d;
-  a.wq = h->wq, a.wscale = h->s_lm;
-  a.ssq_in = h->ssq_a, a.ssq_n = ssq_n, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps;
-  a.out = logits_out, a.ldo = h->Vpad, a.n_valid = h->V;
+  GemvArgs a = dd_gemv_lm_head(h, ssq_n);
+  a.nb = nb, a.out = logits_out;
   if (!lanes) a.state = h->state;      // a finished sequence keeps the logits of its EOS step (the group's fused base rows go
   RC(gemv(EPI_STORE, a));              // to scratch and are handed out by k_scatter_base, which checks per sequence)
   return DD_OK;
@@ -1512,12 +1356,16 @@ static void dbg_sum(int sweep, int n_layers, int layer, int stage, const void* p
 // half_planes), every row goes through the kernels of the plain pass.
 static int lm_sweep_groups(dd_lm* h, dd_lm* const* qs, int ng, int K, hipStream_t st, dd_lm* const* rider = nullptr, int n_rider = 0,
                            bool packed = false) {
-  const int d = h->d, dff = h->dff;
+  const int d = h->d;
   const int planes = n_rider > 0 ? 9 : (packed ? 8 : ng);
   const int hp = packed ? (n_rider > 0 ? 7 : 8) : 0;                  // half planes (with riders: seven of them + two riding planes)
   const int ride_plane0 = packed ? 7 : 8, ride_row0 = 8 * ride_plane0, ride_slot0 = 2 * hp + (ride_plane0 - hp);
   const int rows_g = packed ? 4 : 8;                                  // rows a sequence owns
   auto row0 = [&](int g) -> int { return packed ? 8 * (g >> 1) + 4 * (g & 1) : 8 * g; };
+  auto rows = [&](GemvArgs& a) {                                      // the row geometry and slice scratch of every launch of this sweep
+    a.nb = K, a.n_groups = planes, a.nb_rider = n_rider, a.half_planes = hp;
+    a.part = h->gemv_part, a.part_floats = h->gemv_part_floats;
+  };
   EmbedLanes el;
   memset(&el, 0, sizeof(el));
   for (int g = 0; g < ng; ++g)
@@ -1528,15 +1376,9 @@ static int lm_sweep_groups(dd_lm* h, dd_lm* const* qs, int ng, int K, hipStream_
   dbg_sum(dbg_sweep, h->Lyr, 0, 0, h->xop_d, (size_t)planes * h->S_d * 1024, st);
   int ssq_n = 1;
   for (int l = 0; l < h->Lyr; ++l) {
-    LayerW& w = h->lw[l];
-    GemvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.wf = h->wf;
-    a.W = w.wqkv, a.S = h->S_d, a.n_tiles = h->qkv_tiles, a.nb = K, a.xop = h->xop_d, a.n_groups = planes, a.nb_rider = n_rider, a.half_planes = hp;
-    a.wq = h->wq, a.wscale = w.s_qkv;
-    a.ssq_in = h->ssq_a, a.ssq_n = ssq_n, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps;
-    a.qbuf = h->qbuf, a.q_tiles = h->q_tiles, a.k_tiles = h->k_tiles;
-    a.q_dim = h->q_dim, a.kv_dim = h->kv_dim, a.rope_cos = h->rope_cos, a.rope_sin = h->rope_sin, a.state = qs[0]->state;
+    GemvArgs a = dd_gemv_qkv(h, l, ssq_n);
+    rows(a);
+    a.state = qs[0]->state;
     AttnDecodeArgs t;
     memset(&t, 0, sizeof(t));
     t.wf = h->wf;
@@ -1555,7 +1397,6 @@ static int lm_sweep_groups(dd_lm* h, dd_lm* const* qs, int ng, int K, hipStream_
       if (q->T_host > t.max_T) t.max_T = q->T_host;
     }
     a.knew = a.knew_g[0], a.vnew = a.vnew_g[0], t.knew = t.knew_g[0], t.vnew = t.vnew_g[0];
-    a.part = h->gemv_part, a.part_floats = h->gemv_part_floats;
     float* rk = h->knew + ((size_t)l * KV_ROWS + RIDER_KV_ROW0) * h->kv_dim;
     float* rv = h->vnew + ((size_t)l * KV_ROWS + RIDER_KV_ROW0) * h->kv_dim;
     if (n_rider) {
@@ -1628,47 +1469,28 @@ static int lm_sweep_groups(dd_lm* h, dd_lm* const* qs, int ng, int K, hipStream_
       for (int g = 0; g < ng; ++g) dbg_sum(dbg_sweep, h->Lyr, l, 10, t.vnew_g[g], (size_t)rows_g * h->kv_dim * 4, st);
     }
     dbg_sum(dbg_sweep, h->Lyr, l, 3, h->xop_q, (size_t)planes * h->S_q * 1024, st);
-    memset(&a, 0, sizeof(a));
-    a.wf = h->wf;
-    a.W = w.wo, a.S = h->S_q, a.n_tiles = d / 16, a.nb = K, a.xop = h->xop_q, a.n_groups = planes, a.nb_rider = n_rider, a.half_planes = hp;
-    a.wq = h->wq, a.wscale = w.s_o;
-    a.out = h->xa, a.ldo = d, a.normw_next = w.norm2, a.xop_next = h->xop_d, a.S_next = h->S_d, a.ssq_out = h->ssq_b, a.ssq_ld = d / 16;
-    a.part = h->gemv_part, a.part_floats = h->gemv_part_floats;
+    a = dd_gemv_o(h, l);
+    rows(a);
     RC(on_family(h, st, 2, [&](hipStream_t s2) { return ddk_gemv_groups(EPI_RESID, a, s2); }));
     dbg_sum(dbg_sweep, h->Lyr, l, 4, h->xa, (size_t)8 * planes * d * 4, st);
-    memset(&a, 0, sizeof(a));
-    a.wf = h->wf;
-    a.W = w.wgu, a.S = h->S_d, a.n_tiles = dff / 16, a.nb = K, a.xop = h->xop_d, a.n_groups = planes, a.nb_rider = n_rider, a.half_planes = hp;
-    a.wq = h->wq, a.wscale = w.s_gu;
-    a.ssq_in = h->ssq_b, a.ssq_n = d / 16, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps;
-    a.xop_next = h->xop_ff, a.S_next = h->S_ff;
-    a.part = h->gemv_part, a.part_floats = h->gemv_part_floats;
+    a = dd_gemv_gate_up(h, l);
+    rows(a);
     RC(on_family(h, st, 4, [&](hipStream_t s2) { return ddk_gemv_groups(EPI_SILU, a, s2); }));
     dbg_sum(dbg_sweep, h->Lyr, l, 5, h->xop_ff, (size_t)planes * h->S_ff * 1024, st);
-    memset(&a, 0, sizeof(a));
-    a.wf = h->wf;
-    a.W = w.wdown, a.S = h->S_ff, a.n_tiles = d / 16, a.nb = K, a.xop = h->xop_ff, a.n_groups = planes, a.nb_rider = n_rider, a.half_planes = hp;
-    a.wq = h->wq, a.wscale = w.s_down;
-    a.out = h->xa, a.ldo = d, a.normw_next = (l + 1 < h->Lyr) ? h->lw[l + 1].norm1 : h->final_norm;
-    a.xop_next = h->xop_d, a.S_next = h->S_d, a.ssq_out = h->ssq_a, a.ssq_ld = d / 16;
-    a.part = h->gemv_part, a.part_floats = h->gemv_part_floats;
+    a = dd_gemv_down(h, l);
+    rows(a);
     RC(on_family(h, st, 8, [&](hipStream_t s2) { return ddk_gemv_groups(EPI_RESID, a, s2); }));
     dbg_sum(dbg_sweep, h->Lyr, l, 6, h->xa, (size_t)8 * planes * d * 4, st);
     dbg_sum(dbg_sweep, h->Lyr, l, 7, h->xop_d, (size_t)planes * h->S_d * 1024, st);
     ssq_n = d / 16;
   }
-  GemvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.wf = h->wf;
-  a.W = h->lm_head, a.S = h->S_d, a.n_tiles = h->Vpad / 16, a.nb = K, a.xop = h->xop_d, a.n_groups = planes, a.nb_rider = n_rider, a.half_planes = hp;
-  a.wq = h->wq, a.wscale = h->s_lm;
-  a.ssq_in = h->ssq_a, a.ssq_n = ssq_n, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps;
+  GemvArgs a = dd_gemv_lm_head(h, ssq_n);
+  rows(a);
   for (int g = 0; g < ng; ++g) {
     a.out_g[g] = qs[g]->member_logits;
     for (int m = 0; m < rows_g; ++m) a.state_rows[row0(g) + m] = qs[g]->state;
   }
-  a.out = qs[0]->member_logits, a.ldo = h->Vpad, a.n_valid = h->V;
-  a.part = h->gemv_part, a.part_floats = h->gemv_part_floats;
+  a.out = qs[0]->member_logits;
   if (n_rider) {
     a.out_g[ride_slot0] = h->grp_logits;
     if (n_rider > 8) a.out_g[ride_slot0 + 1] = h->grp_logits + (size_t)8 * h->Vpad;
@@ -2149,7 +1971,7 @@ static int spec_mode_of(const dd_lm* h) { return h->spec_mode >= 0 ? h->spec_mod
 #define SPEC_PROBE_RATE 0.33f     // rate a probe phase starts from: five misses in a row end it
 
 static int lm_sweep_spec(dd_lm* h, int K, hipStream_t st) {
-  const int d = h->d, dff = h->dff;
+  const int d = h->d;
   EmbedLanes el;
   memset(&el, 0, sizeof(el));
   for (int m = 0; m < K; ++m) el.state[m] = h->state;
@@ -2157,21 +1979,14 @@ static int lm_sweep_spec(dd_lm* h, int K, hipStream_t st) {
   RC(ddk_embed_rows_lanes(h->embed, d, el, 16, h->xa, h->lw[0].norm1, h->xop_d, h->ssq_a, d / 16, st, h->wf));
   int ssq_n = 1;
   auto common = [&](GemvArgs& a) {
-    a.nb = K, a.n_groups = 2, a.wq = h->wq, a.state = h->state, a.wf = h->wf;
+    a.nb = K, a.n_groups = 2, a.state = h->state;
     a.part = h->gemv_part, a.part_floats = h->gemv_part_floats;
   };
   for (int l = 0; l < h->Lyr; ++l) {
-    LayerW& w = h->lw[l];
     float* kn = h->knew + (size_t)l * KV_ROWS * h->kv_dim;
     float* vn = h->vnew + (size_t)l * KV_ROWS * h->kv_dim;
-    GemvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.wf = h->wf;
+    GemvArgs a = dd_gemv_qkv(h, l, ssq_n);
     common(a);
-    a.W = w.wqkv, a.S = h->S_d, a.n_tiles = h->qkv_tiles, a.xop = h->xop_d, a.wscale = w.s_qkv;
-    a.ssq_in = h->ssq_a, a.ssq_n = ssq_n, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps;
-    a.qbuf = h->qbuf, a.q_tiles = h->q_tiles, a.k_tiles = h->k_tiles;
-    a.q_dim = h->q_dim, a.kv_dim = h->kv_dim, a.rope_cos = h->rope_cos, a.rope_sin = h->rope_sin;
     a.knew_g[0] = kn, a.vnew_g[0] = vn, a.knew_g[1] = kn + (size_t)8 * h->kv_dim, a.vnew_g[1] = vn + (size_t)8 * h->kv_dim;
     a.knew = kn, a.vnew = vn;
     RC(ddk_gemv_groups(EPI_QKV, a, st));
@@ -2190,36 +2005,21 @@ static int lm_sweep_spec(dd_lm* h, int K, hipStream_t st) {
     t.lane_bits[1] = h->cfg.leak_mask ? h->leak_bits : nullptr;  // un-masked row: InstructBLIP's leaked zeros (bit 0) or nothing
     t.knew = t.knew_g[0], t.vnew = t.vnew_g[0];
     RC(ddk_attn_decode(t, st));
-    memset(&a, 0, sizeof(a));
-    a.wf = h->wf;
+    a = dd_gemv_o(h, l);
     common(a);
-    a.W = w.wo, a.S = h->S_q, a.n_tiles = d / 16, a.xop = h->xop_q, a.wscale = w.s_o;
-    a.out = h->xa, a.ldo = d, a.normw_next = w.norm2, a.xop_next = h->xop_d, a.S_next = h->S_d, a.ssq_out = h->ssq_b, a.ssq_ld = d / 16;
     RC(ddk_gemv_groups(EPI_RESID, a, st));
-    memset(&a, 0, sizeof(a));
-    a.wf = h->wf;
+    a = dd_gemv_gate_up(h, l);
     common(a);
-    a.W = w.wgu, a.S = h->S_d, a.n_tiles = dff / 16, a.xop = h->xop_d, a.wscale = w.s_gu;
-    a.ssq_in = h->ssq_b, a.ssq_n = d / 16, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps;
-    a.xop_next = h->xop_ff, a.S_next = h->S_ff;
     RC(ddk_gemv_groups(EPI_SILU, a, st));
-    memset(&a, 0, sizeof(a));
-    a.wf = h->wf;
+    a = dd_gemv_down(h, l);
     common(a);
-    a.W = w.wdown, a.S = h->S_ff, a.n_tiles = d / 16, a.xop = h->xop_ff, a.wscale = w.s_down;
-    a.out = h->xa, a.ldo = d, a.normw_next = (l + 1 < h->Lyr) ? h->lw[l + 1].norm1 : h->final_norm;
-    a.xop_next = h->xop_d, a.S_next = h->S_d, a.ssq_out = h->ssq_a, a.ssq_ld = d / 16;
     RC(ddk_gemv_groups(EPI_RESID, a, st));
     ssq_n = d / 16;
   }
-  GemvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.wf = h->wf;
+  GemvArgs a = dd_gemv_lm_head(h, ssq_n);
   common(a);
-  a.W = h->lm_head, a.S = h->S_d, a.n_tiles = h->Vpad / 16, a.xop = h->xop_d, a.wscale = h->s_lm;
-  a.ssq_in = h->ssq_a, a.ssq_n = ssq_n, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps;
   a.out_g[0] = h->member_logits, a.out_g[1] = h->grp_logits;   // row 0 of the second group = the un-masked row's logits
-  a.out = h->member_logits, a.ldo = h->Vpad, a.n_valid = h->V;
+  a.out = h->member_logits;
   RC(ddk_gemv_groups(EPI_STORE, a, st));
   return DD_OK;
 }

@@ -1,5 +1,7 @@
 // Engine internals shared by dd_engine.hip and the measurement hooks in dd_tools.hip (libdropdec_tools.so only).
 #pragma once
+#include <string.h>
+
 #include <vector>
 
 #include "dd_lm_kernels.h"
@@ -11,10 +13,12 @@
 #define KV_ROWS 64        // new K/V rows kept per layer: 16 members, or the base rows of up to 64 lanes (group step)
 #define MAX_NEW_TOKENS 8192
 
+// the LM's weight matrices: the four of a layer, and the lm_head (dd_weight below describes them — the ONE place that does)
+enum { DD_M_QKV = 0, DD_M_O, DD_M_GATE_UP, DD_M_DOWN, DD_M_LM_HEAD };
 struct LayerW {
-  u32x4_t *wqkv, *wo, *wgu, *wdown;
+  u32x4_t* w[4] = {nullptr, nullptr, nullptr, nullptr};   // packed tiles, by DD_M_*
+  float* s[4] = {nullptr, nullptr, nullptr, nullptr};     // fp8: per-row scales, packed order; MXFP4: u32 block-scale words
   float *norm1, *norm2;
-  float *s_qkv = nullptr, *s_o = nullptr, *s_gu = nullptr, *s_down = nullptr;   // fp8: per-row scales, packed order; MXFP4: u32 block-scale words
 };
 
 struct dd_lm {
@@ -120,7 +124,6 @@ struct dd_lm {
   size_t rec_scores_ld = 0;
 };
 
-#define KV_ROWS_PER_LAYER KV_ROWS
 // pieces of dd_engine.hip that the tensor-parallel driver (dd_tp.hip) reuses
 int dd_engine_prefill_head(dd_lm* h, const int32_t* row_index, int n_rows, float* logits, hipStream_t st, const float* src);
 int dd_engine_prefill_tail(dd_lm* h, const float* x_rows, int T0, int span_start, int span_len, hipStream_t st);
@@ -142,3 +145,134 @@ int dd_record_launch(dd_lm* const* qs, int n, int K, int mode, hipStream_t st);
 // one packed sweep of nb rows through all layers + lm_head (dd_engine.hip)
 int lm_sweep(dd_lm* h, int nb, const uint8_t* bits, int row0, float* logits_out, hipStream_t st, dd_lm* const* lanes = nullptr,
              const int32_t* skip_if = nullptr);
+
+// -----------------------------------------------------------------------------------------------
+// One description of a weight matrix.  Allocation sizes, the synthetic fill, the loaders' destinations and the W / scale / S /
+// n_tiles of every GEMV and GEMM launch come from dd_weight(); nothing else spells out a matrix's geometry.
+// -----------------------------------------------------------------------------------------------
+struct WMat {
+  u32x4_t* W;      // packed tiles in the handle's storage kind (h->wq)
+  float* scale;    // fp8: one float per packed row; MXFP4: one u32 per row and 128 k; 16-bit storage: nullptr
+  int S;           // K / 32
+  int n_tiles;     // 16-row tiles (gate/up: gate and up tiles interleaved)
+};
+// which: DD_M_*; `layer` is ignored for DD_M_LM_HEAD.  A lane sees its owner's matrices (h->lw / h->lm_head are copies of the owner's).
+static inline WMat dd_weight(const dd_lm* h, int layer, int which) {
+  if (which == DD_M_LM_HEAD) return {h->lm_head, h->s_lm, h->S_d, h->Vpad / 16};
+  const LayerW& w = h->lw[layer];
+  const int S[4] = {h->S_d, h->S_q, h->S_d, h->S_ff};
+  const int n_tiles[4] = {h->qkv_tiles, h->d / 16, 2 * h->dff / 16, h->d / 16};
+  return {w.w[which], w.s[which], S[which], n_tiles[which]};
+}
+// u32x4_t units of the tiles: a tile row holds S * 64 of them in 16-bit storage, half that in fp8, a quarter in MXFP4
+static inline size_t dd_weight_units(const dd_lm* h, const WMat& m) {
+  return (size_t)m.n_tiles * m.S * 64 / (h->wq == DD_WQ_MXFP4 ? 4 : (h->wq ? 2 : 1));
+}
+// entries of `scale` (fp8: floats, MXFP4: u32 words of four e8m0 bytes)
+static inline size_t dd_weight_scales(const dd_lm* h, const WMat& m) {
+  return (size_t)m.n_tiles * 16 * (h->wq == DD_WQ_MXFP4 ? m.S / 4 : 1);
+}
+
+// -----------------------------------------------------------------------------------------------
+// Decode: the GemvArgs of the five launches of a layer sweep, filled with what every sweep agrees on.  The caller adds what is its
+// own: nb / n_groups / nb_rider / half_planes, state / state_rows, knew / vnew / *_g, out / out_g, skip_if, part / part_floats.
+// -----------------------------------------------------------------------------------------------
+// matrix source and operand only (the row-parallel launches of a tensor-parallel shard stop here: dd_tp.hip)
+static inline GemvArgs dd_gemv_matrix(const dd_lm* h, const WMat& m, const u32x4_t* xop) {
+  GemvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.wf = h->wf, a.wq = h->wq;
+  a.W = m.W, a.wscale = m.scale, a.S = m.S, a.n_tiles = m.n_tiles, a.xop = xop;
+  return a;
+}
+// the operand is the un-normalised row: its rstd comes from ssq_n partial sums of squares per row
+static inline void dd_gemv_norm_in(GemvArgs& a, const dd_lm* h, const float* ssq_in, int ssq_n) {
+  a.ssq_in = ssq_in, a.ssq_n = ssq_n, a.ssq_ld = h->d / 16, a.inv_k = 1.0f / h->d, a.eps = h->cfg.rms_eps;
+}
+// EPI_RESID into the residual rows; the next GEMV's operand is normalised with normw_next, its sums of squares go to ssq_out
+static inline void dd_gemv_resid_out(GemvArgs& a, const dd_lm* h, const float* normw_next, float* ssq_out) {
+  a.out = h->xa, a.ldo = h->d, a.normw_next = normw_next, a.xop_next = h->xop_d, a.S_next = h->S_d;
+  a.ssq_out = ssq_out, a.ssq_ld = h->d / 16;
+}
+static inline GemvArgs dd_gemv_qkv(const dd_lm* h, int layer, int ssq_n) {   // ssq_n: 1 after the embedding, d / 16 after a layer
+  GemvArgs a = dd_gemv_matrix(h, dd_weight(h, layer, DD_M_QKV), h->xop_d);
+  dd_gemv_norm_in(a, h, h->ssq_a, ssq_n);
+  a.qbuf = h->qbuf, a.q_tiles = h->q_tiles, a.k_tiles = h->k_tiles, a.q_dim = h->q_dim, a.kv_dim = h->kv_dim;
+  a.rope_cos = h->rope_cos, a.rope_sin = h->rope_sin;
+  return a;
+}
+static inline GemvArgs dd_gemv_o(const dd_lm* h, int layer) {
+  GemvArgs a = dd_gemv_matrix(h, dd_weight(h, layer, DD_M_O), h->xop_q);
+  dd_gemv_resid_out(a, h, h->lw[layer].norm2, h->ssq_b);
+  return a;
+}
+static inline GemvArgs dd_gemv_gate_up(const dd_lm* h, int layer) {
+  GemvArgs a = dd_gemv_matrix(h, dd_weight(h, layer, DD_M_GATE_UP), h->xop_d);
+  a.n_tiles /= 2;                                                   // EPI_SILU counts gate/up PAIRS
+  dd_gemv_norm_in(a, h, h->ssq_b, h->d / 16);
+  a.xop_next = h->xop_ff, a.S_next = h->S_ff;
+  return a;
+}
+static inline GemvArgs dd_gemv_down(const dd_lm* h, int layer) {     // the norm that follows: the next layer's first, or the final one
+  GemvArgs a = dd_gemv_matrix(h, dd_weight(h, layer, DD_M_DOWN), h->xop_ff);
+  dd_gemv_resid_out(a, h, layer + 1 < h->Lyr ? h->lw[layer + 1].norm1 : h->final_norm, h->ssq_a);
+  return a;
+}
+static inline GemvArgs dd_gemv_lm_head(const dd_lm* h, int ssq_n) {
+  GemvArgs a = dd_gemv_matrix(h, dd_weight(h, 0, DD_M_LM_HEAD), h->xop_d);
+  dd_gemv_norm_in(a, h, h->ssq_a, ssq_n);
+  a.ldo = h->Vpad, a.n_valid = h->V;
+  return a;
+}
+
+// -----------------------------------------------------------------------------------------------
+// Prefill: the GemmArgs of the same five launches over M rows in the A planes a_hi / a_lo (the caller's scratch: the solo p1 / p2
+// planes or the batch's pb planes).  The caller adds the destination (out, qbuf, kc / vc, o_hi / o_lo, pos0, the seq_* table)
+// and points the launch at its matrix with dd_gemm_weight.
+// -----------------------------------------------------------------------------------------------
+static inline GemmArgs dd_gemm_rows(const dd_lm* h, const WMat& m, const uint16_t* a_hi, const uint16_t* a_lo, int M) {
+  GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.wf = h->wf;
+  g.a_hi = a_hi, g.a_lo = a_lo, g.M = M, g.S = m.S, g.n_tiles = m.n_tiles;
+  return g;
+}
+static inline GemmArgs dd_gemm_qkv(const dd_lm* h, int layer, const uint16_t* a_hi, const uint16_t* a_lo, int M) {
+  GemmArgs g = dd_gemm_rows(h, dd_weight(h, layer, DD_M_QKV), a_hi, a_lo, M);
+  g.T_cap = h->T_cap, g.q_tiles = h->q_tiles, g.k_tiles = h->k_tiles, g.q_dim = h->q_dim, g.kv_dim = h->kv_dim, g.kv16 = h->kv16;
+  g.rope_cos = h->rope_cos, g.rope_sin = h->rope_sin;
+  return g;
+}
+static inline GemmArgs dd_gemm_o(const dd_lm* h, int layer, const uint16_t* a_hi, const uint16_t* a_lo, int M) {
+  GemmArgs g = dd_gemm_rows(h, dd_weight(h, layer, DD_M_O), a_hi, a_lo, M);
+  g.ldo = h->d;
+  return g;
+}
+static inline GemmArgs dd_gemm_gate_up(const dd_lm* h, int layer, const uint16_t* a_hi, const uint16_t* a_lo, int M) {
+  GemmArgs g = dd_gemm_rows(h, dd_weight(h, layer, DD_M_GATE_UP), a_hi, a_lo, M);
+  g.ld_planes = h->dff;
+  return g;
+}
+static inline GemmArgs dd_gemm_down(const dd_lm* h, int layer, const uint16_t* a_hi, const uint16_t* a_lo, int M) {
+  GemmArgs g = dd_gemm_rows(h, dd_weight(h, layer, DD_M_DOWN), a_hi, a_lo, M);
+  g.ldo = h->d;
+  return g;
+}
+static inline GemmArgs dd_gemm_lm_head(const dd_lm* h, const uint16_t* a_hi, const uint16_t* a_lo, int M) {
+  GemmArgs g = dd_gemm_rows(h, dd_weight(h, 0, DD_M_LM_HEAD), a_hi, a_lo, M);
+  g.ldo = h->Vpad, g.n_valid = h->V;
+  return g;
+}
+// g.W / g.wscale for matrix `which` of `layer`.  fp8 / MXFP4 storage: the GEMM runs on a bf16 expansion of ONE matrix at a time
+// (exact) in h->deq_tmp, enqueued here; fp8 row scales go to the GEMM's epilogue, MXFP4 block scales are applied by the expansion.
+static inline int dd_gemm_weight(const dd_lm* h, int layer, int which, GemmArgs& g, hipStream_t st) {
+  const WMat m = dd_weight(h, layer, which);
+  if (!h->wq) {
+    g.W = m.W;
+    return DD_OK;
+  }
+  g.W = h->deq_tmp;
+  if (h->wq == DD_WQ_MXFP4) return ddk_dequant_tiles_mxfp4(m.W, (const uint32_t*)m.scale, h->deq_tmp, m.n_tiles, m.S, st);
+  g.wscale = m.scale;
+  return ddk_dequant_tiles(m.W, h->deq_tmp, m.n_tiles, m.S, st);
+}

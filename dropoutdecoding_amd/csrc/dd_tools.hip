@@ -46,32 +46,17 @@ extern "C" int dd_lm_time_gemv(dd_lm* h, int which, int nb, int iters, float* me
     a.part = h->gemv_part, a.part_floats = h->gemv_part_floats;
     return wide ? ddk_gemv_groups(epi, a, st) : ddk_gemv(epi, a, st);
   };
-  const int d = h->d, dff = h->dff;
-  auto launch = [&](int l) -> int {
-    LayerW& w = h->lw[l % h->Lyr];
+  auto launch = [&](int i) -> int {
+    const int l = i % h->Lyr;
     GemvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.wf = h->wf;
-    a.nb = nb, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps, a.state = h->state, a.wq = h->wq;
     switch (which) {
-      case 0:
-        a.W = w.wqkv, a.wscale = w.s_qkv, a.S = h->S_d, a.n_tiles = h->qkv_tiles, a.xop = h->xop_d, a.ssq_in = h->ssq_a, a.ssq_n = d / 16, a.ssq_ld = d / 16;
-        a.qbuf = h->qbuf, a.knew = h->knew, a.vnew = h->vnew, a.q_tiles = h->q_tiles, a.k_tiles = h->k_tiles;
-        a.q_dim = h->q_dim, a.kv_dim = h->kv_dim, a.rope_cos = h->rope_cos, a.rope_sin = h->rope_sin;
-        return gemv(EPI_QKV, a);
-      case 1:
-        a.W = w.wo, a.wscale = w.s_o, a.S = h->S_q, a.n_tiles = d / 16, a.xop = h->xop_q, a.out = h->xa, a.ldo = d;
-        a.normw_next = w.norm2, a.xop_next = h->xop_d, a.ssq_out = h->ssq_b, a.ssq_ld = d / 16;
-        return gemv(EPI_RESID, a);
-      case 2:
-        a.W = w.wgu, a.wscale = w.s_gu, a.S = h->S_d, a.n_tiles = dff / 16, a.xop = h->xop_d, a.ssq_in = h->ssq_b, a.ssq_n = d / 16, a.ssq_ld = d / 16;
-        a.xop_next = h->xop_ff;
-        return gemv(EPI_SILU, a);
-      default:
-        a.W = w.wdown, a.wscale = w.s_down, a.S = h->S_ff, a.n_tiles = d / 16, a.xop = h->xop_ff, a.out = h->xa, a.ldo = d;
-        a.normw_next = w.norm1, a.xop_next = h->xop_d, a.ssq_out = h->ssq_a, a.ssq_ld = d / 16;
-        return gemv(EPI_RESID, a);
+      case 0: a = dd_gemv_qkv(h, l, h->d / 16), a.knew = h->knew, a.vnew = h->vnew; break;
+      case 1: a = dd_gemv_o(h, l); break;
+      case 2: a = dd_gemv_gate_up(h, l); break;
+      default: a = dd_gemv_down(h, l), a.normw_next = h->lw[l].norm1; break;   // (any norm vector does for a timing)
     }
+    a.nb = nb, a.inv_k = 1.0f / h->d, a.eps = h->cfg.rms_eps, a.state = h->state;
+    return gemv(which == 0 ? EPI_QKV : (which == 2 ? EPI_SILU : EPI_RESID), a);
   };
   for (int i = 0; i < h->Lyr; ++i) RC(launch(i));  // warm (also evicts)
   DD_HIP(hipEventRecord(h->ev0, st));
@@ -81,6 +66,7 @@ extern "C" int dd_lm_time_gemv(dd_lm* h, int which, int nb, int iters, float* me
   float ms = 0;
   DD_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
   *mean_ms = ms / iters;
+  const int d = h->d, dff = h->dff;
   double rows[4] = {(double)(h->q_dim + 2 * h->kv_dim) * d, (double)d * h->q_dim, 2.0 * dff * d, (double)d * dff};
   *bytes_per_launch = rows[which] * (h->wq == DD_WQ_MXFP4 ? 0.5 + 1.0 / 32.0 : (h->wq ? 1.0 : 2.0));
   return DD_OK;

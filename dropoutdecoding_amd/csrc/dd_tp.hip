@@ -105,19 +105,14 @@ static int tp_prefill_layers(dd_lm* const* R, int n, int T0, hipStream_t st) {
       dd_lm* h = R[r];
       LayerW& w = h->lw[l];
       RC(ddk_rmsnorm_split(h->px, T0, d, w.norm1, h->cfg.rms_eps, h->p1_hi, h->p1_lo, nullptr, nullptr, st, h->wf));
-      GemmArgs g;
-      memset(&g, 0, sizeof(g));
-      g.wf = h->wf;
-      g.a_hi = h->p1_hi, g.a_lo = h->p1_lo, g.M = T0, g.S = h->S_d, g.n_tiles = h->qkv_tiles, g.W = w.wqkv;
-      g.qbuf = h->pq, g.kc = h->kc + (size_t)l * h->lsk, g.vc = h->vc + (size_t)l * h->lsv, g.T_cap = h->T_cap;
-      g.q_tiles = h->q_tiles, g.k_tiles = h->k_tiles, g.q_dim = h->q_dim, g.kv_dim = h->kv_dim, g.pos0 = 0, g.kv16 = h->kv16;
-      g.rope_cos = h->rope_cos, g.rope_sin = h->rope_sin;
+      GemmArgs g = dd_gemm_qkv(h, l, h->p1_hi, h->p1_lo, T0);
+      RC(dd_gemm_weight(h, l, DD_M_QKV, g, st));             // (a shard stores 16-bit weights: nothing is expanded)
+      g.qbuf = h->pq, g.kc = h->kc + (size_t)l * h->lsk, g.vc = h->vc + (size_t)l * h->lsv;
       RC(ddk_gemm(EPI_QKV, g, st));
       RC(ddk_attn_prefill(h->pq, g.kc, g.vc, T0, h->T_cap, h->H, h->Hkv, h->p1_hi, h->p1_lo, nullptr, 0, 0, 0, 0, st, nullptr, h->kv16, h->wf));
-      memset(&g, 0, sizeof(g));
-      g.wf = h->wf;
-      g.a_hi = h->p1_hi, g.a_lo = h->p1_lo, g.M = T0, g.S = h->S_q, g.n_tiles = d / 16, g.W = w.wo;
-      g.out = h->tp_gather + (size_t)h->tp_rank * slot, g.ldo = d, g.n_valid = d;       // this rank's partial o_proj product
+      g = dd_gemm_o(h, l, h->p1_hi, h->p1_lo, T0);
+      RC(dd_gemm_weight(h, l, DD_M_O, g, st));
+      g.out = h->tp_gather + (size_t)h->tp_rank * slot, g.n_valid = d;       // this rank's partial o_proj product
       RC(ddk_gemm(EPI_STORE, g, st));
     }
     RC(tp_seam(R, n, T0, st));
@@ -127,16 +122,13 @@ static int tp_prefill_layers(dd_lm* const* R, int n, int T0, hipStream_t st) {
       dd_lm* h = R[r];
       LayerW& w = h->lw[l];
       RC(ddk_rmsnorm_split(h->px, T0, d, w.norm2, h->cfg.rms_eps, h->p1_hi, h->p1_lo, nullptr, nullptr, st, h->wf));
-      GemmArgs g;
-      memset(&g, 0, sizeof(g));
-      g.wf = h->wf;
-      g.a_hi = h->p1_hi, g.a_lo = h->p1_lo, g.M = T0, g.S = h->S_d, g.n_tiles = 2 * h->dff / 16, g.W = w.wgu;
-      g.o_hi = h->p2_hi, g.o_lo = h->p2_lo, g.ld_planes = h->dff;
+      GemmArgs g = dd_gemm_gate_up(h, l, h->p1_hi, h->p1_lo, T0);
+      RC(dd_gemm_weight(h, l, DD_M_GATE_UP, g, st));
+      g.o_hi = h->p2_hi, g.o_lo = h->p2_lo;
       RC(ddk_gemm(EPI_SILU, g, st));
-      memset(&g, 0, sizeof(g));
-      g.wf = h->wf;
-      g.a_hi = h->p2_hi, g.a_lo = h->p2_lo, g.M = T0, g.S = h->S_ff, g.n_tiles = d / 16, g.W = w.wdown;
-      g.out = h->tp_gather + (size_t)h->tp_rank * slot, g.ldo = d, g.n_valid = d;
+      g = dd_gemm_down(h, l, h->p2_hi, h->p2_lo, T0);
+      RC(dd_gemm_weight(h, l, DD_M_DOWN, g, st));
+      g.out = h->tp_gather + (size_t)h->tp_rank * slot, g.n_valid = d;
       RC(ddk_gemm(EPI_STORE, g, st));
     }
     RC(tp_seam(R, n, T0, st));
@@ -176,16 +168,10 @@ static int tp_sweep(dd_lm* const* R, int n, int nb, const uint8_t* const* bits, 
   for (int l = 0; l < h0->Lyr; ++l) {
     for (int r = 0; r < n; ++r) {
       dd_lm* h = R[r];
-      LayerW& w = h->lw[l];
-      float* knew = h->knew + ((size_t)l * KV_ROWS_PER_LAYER + row0) * h->kv_dim;
-      float* vnew = h->vnew + ((size_t)l * KV_ROWS_PER_LAYER + row0) * h->kv_dim;
-      GemvArgs a;
-      memset(&a, 0, sizeof(a));
-      a.wf = h->wf;
-      a.W = w.wqkv, a.S = h->S_d, a.n_tiles = h->qkv_tiles, a.nb = nb, a.xop = h->xop_d;
-      a.ssq_in = h->ssq_a, a.ssq_n = ssq_n, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps;
-      a.qbuf = h->qbuf, a.knew = knew, a.vnew = vnew, a.q_tiles = h->q_tiles, a.k_tiles = h->k_tiles;
-      a.q_dim = h->q_dim, a.kv_dim = h->kv_dim, a.rope_cos = h->rope_cos, a.rope_sin = h->rope_sin, a.state = h->state;
+      float* knew = h->knew + ((size_t)l * KV_ROWS + row0) * h->kv_dim;
+      float* vnew = h->vnew + ((size_t)l * KV_ROWS + row0) * h->kv_dim;
+      GemvArgs a = dd_gemv_qkv(h, l, ssq_n);
+      a.nb = nb, a.knew = knew, a.vnew = vnew, a.state = h->state;
       RC(ddk_gemv(EPI_QKV, a, st));
       AttnDecodeArgs t;
       memset(&t, 0, sizeof(t));
@@ -196,10 +182,9 @@ static int tp_sweep(dd_lm* const* R, int n, int nb, const uint8_t* const* bits, 
       t.span_start = h->span_start, t.span_len = h->L, t.part_o = h->part_o, t.part_ml = h->part_ml;
       t.knew = knew, t.vnew = vnew, t.xop_out = h->xop_q;
       RC(ddk_attn_decode(t, st));
-      memset(&a, 0, sizeof(a));
-      a.wf = h->wf;
-      a.W = w.wo, a.S = h->S_q, a.n_tiles = d / 16, a.nb = nb, a.xop = h->xop_q;
-      a.out = h->tp_gather + (size_t)h->tp_rank * slot, a.ldo = d, a.n_valid = d;          // partial o_proj product
+      // row-parallel: the plain product goes to this rank's slot, the seam runs the epilogue (so no dd_gemv_o / dd_gemv_down here)
+      a = dd_gemv_matrix(h, dd_weight(h, l, DD_M_O), h->xop_q);
+      a.nb = nb, a.out = h->tp_gather + (size_t)h->tp_rank * slot, a.ldo = d, a.n_valid = d;
       RC(ddk_gemv(EPI_STORE, a, st));
     }
     RC(tp_seam(R, n, nb, st));
@@ -208,17 +193,11 @@ static int tp_sweep(dd_lm* const* R, int n, int nb, const uint8_t* const* bits, 
       RC(ddk_tp_finish(R[r]->tp_gather, W, slot, nb, R[r]->xa, d, R[r]->lw[l].norm2, R[r]->xop_d, R[r]->ssq_b, d / 16, R[r]->wf, st));
     for (int r = 0; r < n; ++r) {
       dd_lm* h = R[r];
-      LayerW& w = h->lw[l];
-      GemvArgs a;
-      memset(&a, 0, sizeof(a));
-      a.wf = h->wf;
-      a.W = w.wgu, a.S = h->S_d, a.n_tiles = h->dff / 16, a.nb = nb, a.xop = h->xop_d;
-      a.ssq_in = h->ssq_b, a.ssq_n = d / 16, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps, a.xop_next = h->xop_ff, a.S_next = h->S_ff;
+      GemvArgs a = dd_gemv_gate_up(h, l);
+      a.nb = nb;
       RC(ddk_gemv(EPI_SILU, a, st));
-      memset(&a, 0, sizeof(a));
-      a.wf = h->wf;
-      a.W = w.wdown, a.S = h->S_ff, a.n_tiles = d / 16, a.nb = nb, a.xop = h->xop_ff;
-      a.out = h->tp_gather + (size_t)h->tp_rank * slot, a.ldo = d, a.n_valid = d;
+      a = dd_gemv_matrix(h, dd_weight(h, l, DD_M_DOWN), h->xop_ff);
+      a.nb = nb, a.out = h->tp_gather + (size_t)h->tp_rank * slot, a.ldo = d, a.n_valid = d;
       RC(ddk_gemv(EPI_STORE, a, st));
     }
     RC(tp_seam(R, n, nb, st));
@@ -231,12 +210,8 @@ static int tp_sweep(dd_lm* const* R, int n, int nb, const uint8_t* const* bits, 
   }
   for (int r = 0; r < n; ++r) {          // lm_head: replicated (2 % of the weights), every rank holds the full logits
     dd_lm* h = R[r];
-    GemvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.wf = h->wf;
-    a.W = h->lm_head, a.S = h->S_d, a.n_tiles = h->Vpad / 16, a.nb = nb, a.xop = h->xop_d;
-    a.ssq_in = h->ssq_a, a.ssq_n = ssq_n, a.ssq_ld = d / 16, a.inv_k = 1.0f / d, a.eps = h->cfg.rms_eps;
-    a.out = logits[r], a.ldo = h->Vpad, a.n_valid = h->V, a.state = h->state;
+    GemvArgs a = dd_gemv_lm_head(h, ssq_n);
+    a.nb = nb, a.out = logits[r], a.state = h->state;
     RC(ddk_gemv(EPI_STORE, a, st));
   }
   return DD_OK;
