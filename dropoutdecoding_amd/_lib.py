@@ -27,7 +27,7 @@ SYMBOLS = [
 
 # include/dropdec_tools.h: libdropdec_tools.so only (bench.py's roofline leg, tools/)
 TOOLS_LIB_PATH = os.path.join(_HERE, "libdropdec_tools.so")
-TOOLS_SYMBOLS = ["dd_lm_time_sweep", "dd_lm_time_gemv", "dd_tools_last_gemv_kernel", "dd_hbm_read_bench", "dd_tools_set_tuning",
+TOOLS_SYMBOLS = ["dd_lm_time_sweep", "dd_lm_time_gemv", "dd_tools_last_gemv_kernel", "dd_tools_gemv_plan", "dd_hbm_read_bench", "dd_tools_set_tuning",
                  "dd_tools_trace_attach", "dd_tools_lds_poison", "dd_tools_scratch_probe", "dd_tools_sample_masks_lanes", "dd_tools_sweep_trace", "dd_tools_attn_trace", "dd_tools_lds_barrier_probe", "dd_tools_lds_overlap_probe", "dd_tools_hold_probe", "dd_tools_pk_probe", "dd_tools_pv_probe", "dd_tools_pkadd_gload_probe", "dd_tools_twist_probe", "dd_tools_barrier_probe", "dd_tools_pk_war_probe",
                  "dd_tools_sampler_dbg_attach", "dd_tools_sampler_dbg_words", "dd_tools_sampler_dbg_launches",
                  "dd_tools_stream_create_cu_mask", "dd_tools_stream_destroy", "dd_tools_cu_probe"]
@@ -73,7 +73,7 @@ def load() -> C.CDLL:
         return _lib
     if os.environ.get("DD_USE_TOOLS_LIB", "0") not in ("", "0"):
         _lib = load_tools()                # the scripts under tools/: one library for the whole process
-        for kv in os.environ.get("DD_TOOLS_TUNE", "").replace(";", ",").split(","):      # A/B runs of bench.py: DD_TOOLS_TUNE="38=1,18=-2"
+        for kv in os.environ.get("DD_TOOLS_TUNE", "").replace(";", ",").split(","):      # A/B runs of bench.py: DD_TOOLS_TUNE="38=1,54=0"
             if "=" in kv:
                 k, v = kv.split("=")
                 _lib.dd_tools_set_tuning(int(k), int(v))
@@ -93,6 +93,7 @@ def load_tools() -> C.CDLL:
         lib.dd_lm_time_sweep.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float), vp]
         lib.dd_lm_time_gemv.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_double), vp]
         lib.dd_tools_last_gemv_kernel.restype = C.c_char_p
+        lib.dd_tools_gemv_plan.argtypes = [C.c_int] * 7 + [C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         lib.dd_hbm_read_bench.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_float), vp]
         lib.dd_tools_set_tuning.argtypes = [C.c_int, C.c_int]
         lib.dd_tools_trace_attach.argtypes = [vp, vp, C.c_int, vp]

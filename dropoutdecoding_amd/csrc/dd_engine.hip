@@ -1584,7 +1584,7 @@ __global__ __launch_bounds__(256) void k_scatter_base(const float* grp_logits, c
 // -----------------------------------------------------------------------------------------------
 // Rider form of the group step (16, 24, ... 64 sequences in groups of eight, K <= 8, fp16 cache, 16-bit weights of the 7B shapes).
 // The un-masked rows of a group step do not need a sweep of their own: a 64-row member sweep streams every weight anyway, and
-// eight more rows are a ninth operand plane of the same kernels (dd_gemv.hip try_slices9).  The groups of a branch form a ring
+// eight more rows are a ninth operand plane of the same kernels (dd_gemv.hip plan_slices).  The groups of a branch form a ring
 // c0, c1, ... : the sweep of c_j carries the members of c_j AND the un-masked rows of c_(j+1) — whose previous token was voted a
 // step ago (or, for the last sweep of the ring, the rows of c0's NEXT step: c0's token of this step was voted in the ring's first
 // sweep).  c_(j+1)'s masks are sampled when that sweep ends, its members run next.  c0's rows for the next step are parked in
@@ -1626,7 +1626,7 @@ static int rider_branches(dd_lm* const* lanes, int n, int K, int* gs_out = nullp
   if (gs_out) *gs_out = gs;
   dd_lm* h0 = lanes[0];
   if (!h0->kv16 || !h0->gemv_part) return 0;
-  // shapes with nine-plane kernels (dd_gemv.hip try_slices9 / try_slices9_fp8)
+  // shapes with nine-plane kernels (dd_gemv.hip plan_slices)
   const int qt = h0->qkv_tiles, gt = 2 * h0->dff / 16;
   if (h0->wq == DD_WQ_MXFP4) return 0;   // MXFP4 tiles have no nine-plane kernels: the classic form
   if (h0->wq) {                 // fp8 tiles: K = 4096 for qkv / o / gate-up / lm_head, K = 14336 for down (Mistral-7B: BASELINE config 5)

@@ -302,42 +302,6 @@ __global__ __launch_bounds__(GEMV_THREADS) void k_gemv(GemvArgs a) {
       }
     }
   }
-  if constexpr (!WQ && PIPE == 1) {
-    // Ring of U requests per wave: slot u is consumed by its MFMA and immediately re-requested U steps ahead, so the
-    // wave always has ~U weight tiles in flight (no drain between batches).
-    const int n = spw;
-    u32x4_t b[U], w[TILES][U];
-    auto req = [&](int u, int step) {
-#pragma unroll
-      for (int t = 0; t < TILES; ++t) w[t][u] = ldw(wp[t] + (size_t)step * SS * 64);
-      b[u] = xp[(size_t)step * SS * 64];
-    };
-    auto use = [&](int u) {
-#pragma unroll
-      for (int t = 0; t < TILES; ++t)
-        acc[t] = dd_mfma16<WF>(w[t][u], b[u], acc[t]);
-    };
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      if (u < n) req(u, u);
-    int s = 0;
-    for (; s + 2 * U <= n; s += U) {
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        use(u);
-        req(u, s + U + u);
-        __builtin_amdgcn_sched_barrier(0);   // keep consume -> re-request order (otherwise the scheduler sinks all
-      }                                      // requests below the last MFMA, which is the batch order again)
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if (s + u < n) use(u);
-      if (s + U + u < n) req(u, s + U + u);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      if (s + U + u < n) use(u);
-  }
 
   late_prefetch();
   finish_rstd();
@@ -486,35 +450,19 @@ int ddk_tp_finish(const float* gather, int W, size_t slot_floats, int nb, float*
   return DD_OK;
 }
 
-// tuning knobs (dd_set_tuning): 0 = U (4/8/16), 4 = ring (1) or batch (0) request order.
-// Keys 1 (non-temporal loads) and 2 (k-step interleave) are settled at 1 and kept only as accepted no-ops.
-static int g_gemv_u = 8, g_gemv_pipe = 0;
-void ddk_set_tuning(int key, int value) {
-  if (key == 0) g_gemv_u = value;
-  else if (key == 4) g_gemv_pipe = value;
-}
-
 // name (as a kernel trace prints it) of the streaming kernel the last ddk_gemv / ddk_gemv_groups call of this thread launched
 static thread_local char g_last_kernel[96] = "";
 const char* ddk_last_gemv_kernel() { return g_last_kernel; }
 #define NOTE_KERNEL(...) snprintf(g_last_kernel, sizeof(g_last_kernel), __VA_ARGS__)
 
 template <int EPI, int TILES>
-static void launch_gemv(const GemvArgs& a_, hipStream_t st) {
-  const GemvArgs& a = a_;
-  NOTE_KERNEL("k_gemv<%d, %d, %d, 1, 1, %d, %d, %d>", EPI, TILES, a.wq ? 8 : (g_gemv_u == 4 || g_gemv_u == 16 ? g_gemv_u : 8), a.wq,
-              a.wq ? 0 : (g_gemv_pipe ? 1 : 0), a.wq ? 0 : (a.wf ? 1 : 0));
-#define GV(U_, P_)                                                                             \
-  do {                                                                                         \
-    if (a.wf) k_gemv<EPI, TILES, U_, 1, 1, 0, P_, 1><<<a.n_tiles, GEMV_THREADS, 0, st>>>(a);   \
-    else k_gemv<EPI, TILES, U_, 1, 1, 0, P_, 0><<<a.n_tiles, GEMV_THREADS, 0, st>>>(a);        \
-  } while (0)
-  if (a.wq == DD_WQ_MXFP4) { k_gemv<EPI, TILES, 8, 1, 1, DD_WQ_MXFP4><<<a.n_tiles, GEMV_THREADS, 0, st>>>(a); return; }
-  if (a.wq) { k_gemv<EPI, TILES, 8, 1, 1, DD_WQ_FP8><<<a.n_tiles, GEMV_THREADS, 0, st>>>(a); return; }
-  const int u = g_gemv_u;
-  if (g_gemv_pipe) { if (u == 4) GV(4, 1); else if (u == 16) GV(16, 1); else GV(8, 1); }
-  else { if (u == 4) GV(4, 0); else if (u == 16) GV(16, 0); else GV(8, 0); }
-#undef GV
+static void launch_gemv(const GemvArgs& a, hipStream_t st) {
+  // 16-bit weights: eight weight tiles per wave, requested as a batch (k_gemv's U = 8, PIPE = 0)
+  NOTE_KERNEL("k_gemv<%d, %d, 8, 1, 1, %d, 0, %d>", EPI, TILES, a.wq, a.wq ? 0 : (a.wf ? 1 : 0));
+  if (a.wq == DD_WQ_MXFP4) k_gemv<EPI, TILES, 8, 1, 1, DD_WQ_MXFP4><<<a.n_tiles, GEMV_THREADS, 0, st>>>(a);
+  else if (a.wq) k_gemv<EPI, TILES, 8, 1, 1, DD_WQ_FP8><<<a.n_tiles, GEMV_THREADS, 0, st>>>(a);
+  else if (a.wf) k_gemv<EPI, TILES, 8, 1, 1, 0, 0, 1><<<a.n_tiles, GEMV_THREADS, 0, st>>>(a);
+  else k_gemv<EPI, TILES, 8, 1, 1, 0, 0, 0><<<a.n_tiles, GEMV_THREADS, 0, st>>>(a);
 }
 
 int g_gemv_loop = 1;            // dd_tools_set_tuning key 54: k_gemv_loop for the K = 4096 matrices of an 8-row pass (0: k_gemv; n > 1: n workgroups)
@@ -564,8 +512,7 @@ int ddk_gemv(int epi, const GemvArgs& a, hipStream_t st) {
 // tile step (the kernel is HBM-bound; even 4 planes keep the MFMA pipe under half busy).
 // ===============================================================================================
 
-// What the epilogue needs from memory, requested before the weight stream (k_gemv_groups) or before the partial sums
-// (k_gemv_finish): residual + next norm weight (EPI_RESID), rotary cos/sin (EPI_QKV), the finished flag (EPI_STORE).
+// What k_gemv_groups' epilogue needs from memory: residual + next norm weight (EPI_RESID), rotary cos/sin (EPI_QKV), the finished flag (EPI_STORE).
 // Epilogue thread t < 128 * NG: group t >> 7, row m = 8 * group + (t & 7), column n = (t & 127) >> 3.
 template <int TILES>
 struct GroupsPre {
@@ -852,55 +799,13 @@ __global__ __launch_bounds__(GEMV_THREADS) void k_gemv_groups(GemvArgs a) {
   groups_epilogue<EPI, TILES, NG>(a, blockIdx.x, pre, rstd_sh, ssq_sh, tile_sum);
 }
 
-// Second half of the slice-resident GEMV (dd_gemv_slices.h): adds the slices' partial sums in k_gemv's order and runs
-// k_gemv_groups' epilogue for ONE tile set per workgroup (128 * NG threads).  Everything it needs from memory — the
-// partial sums, rstd (assembled by the first kernel), residual / norm weight / rotary terms — is requested up front.
+// Second half of the slice-resident GEMV (dd_gemv_slices.h): adds the slices' partial sums in k_gemv's order and runs the epilogue of
+// k_gemv_groups (the same operations per output in the same order: the same bits) for ONE tile set per workgroup.  Everything it needs from
+// memory — the partial sums, rstd (assembled by the first kernel), residual / norm weight / rotary terms — is requested up front.
 // part: [NP][n_tiles_total][NG][128], NP = 8 (single slices) or 4 (slice pairs already added by the producer).
-template <int EPI, int TILES, int NG, int NP>
-__global__ __launch_bounds__(128 * NG) void k_gemv_finish(GemvArgs a, const float* __restrict__ part, const float* __restrict__ rstd_g,
-                                                          int n_sets) {
-  __shared__ float ssq_sh[16 * 8 * NG];
-  __shared__ float rstd_sh[8 * NG];
-  __shared__ float y_sh[EPI == EPI_QKV ? TILES * 128 * NG : 1];   // rotary tiles: a thread needs its partner column's sum (n ^ 8)
-  const int wg = blockIdx.x, tile0 = wg * TILES;
-  const int et = threadIdx.x, eg = et >> 7, ml = et & 7, en = (et & 127) >> 3;
-  const size_t ps = ((size_t)n_sets * TILES * NG) << 7;
-  // one batch of requests: the thread's partial sums, rstd, the epilogue's operands — a single memory round trip before the
-  // arithmetic
-  float v[TILES][NP];
-#pragma unroll
-  for (int tt = 0; tt < TILES; ++tt) {
-    const float* p0 = part + (((size_t)(tile0 + tt) * NG + eg) << 7) + dd_part_index(en, ml);
-#pragma unroll
-    for (int q = 0; q < NP; ++q) v[tt][q] = p0[(size_t)q * ps];
-  }
-  if (a.ssq_in && et < 8 * NG) rstd_sh[et] = rstd_g[et];
-  GroupsPre<TILES> pre;
-  groups_prefetch<EPI, TILES, NG>(a, tile0, pre);
-  float y_own[TILES];
-#pragma unroll
-  for (int tt = 0; tt < TILES; ++tt) {
-    float y = 0.f;
-    if (NP == 8) {
-#pragma unroll
-      for (int q = 0; q < 8; q += 2) y += v[tt][q] + v[tt][q + 1];
-    } else {
-#pragma unroll
-      for (int q = 0; q < NP; ++q) y += v[tt][q];
-    }
-    y_own[tt] = y;
-    if (EPI == EPI_QKV) y_sh[tt * 128 * NG + et] = y;   // the partner (same group and row, column n ^ 8) is thread et ^ 64
-  }
-  __syncthreads();                                   // rstd_sh, y_sh
-  auto tile_sum = [&](int tt, int n) -> float { return (EPI == EPI_QKV && n != en) ? y_sh[tt * 128 * NG + (et ^ 64)] : y_own[tt]; };
-  groups_epilogue<EPI, TILES, NG>(a, wg, pre, rstd_sh, ssq_sh, tile_sum);
-}
-
-// The same finishing step with FOUR output columns per thread: one 16-byte load per partial-sum slab instead of four 4-byte
-// ones (the slabs' element order — dd_part_index — keeps columns n & 3 adjacent), 16-byte residual / logits accesses, 8-byte
-// operand stores, the rotary partner column (n ^ 8) by one wave shuffle.  32 * NG threads per tile set: thread = (plane eg,
-// column quad c4 = columns 4 c4 .. 4 c4 + 3, row ml).  Every output is computed by the same operations in the same order as in
-// k_gemv_finish (and so as in k_gemv / k_gemv_groups): the bits do not change.
+// FOUR output columns per thread: one 16-byte load per partial-sum slab (the slabs' element order — dd_part_index — keeps columns n & 3
+// adjacent), 16-byte residual / logits accesses, 8-byte operand stores, the rotary partner columns (n ^ 8) through LDS.  32 * NG threads
+// per tile set: thread = (plane eg, column quad c4 = columns 4 c4 .. 4 c4 + 3, row ml).
 __device__ __forceinline__ void xop_store16x4(u32x4_t* xop, int k0, int m, const float (&y)[4], int S, int wf) {
   uint32_t hi[4], lo[4];
 #pragma unroll
@@ -1093,30 +998,210 @@ static int launch_gemv_groups(const GemvArgs& a, hipStream_t st) {
   return a.wq ? launch_gemv_groups_f<EPI, TILES, NG, DD_WQ_FP8>(a, st) : launch_gemv_groups_f<EPI, TILES, NG, 0>(a, st);
 }
 
-// ---- slice-resident path (dd_gemv_slices.h + k_gemv_finish): bf16 weights, the per-layer matrices at the shapes the 7B
-// families have (K = 4096: 16 k-steps per slice; K = 11008 / 14336: 43 / 56, staged in chunks of 16).  Anything else runs
-// through k_gemv_groups; both produce the same bits.
+// ---- slice-resident path (dd_gemv_slices.h + k_gemv_finish4): bf16 / fp16 / fp8 weights, the per-layer matrices at the shapes the 7B
+// families have (K = 4096: 16 k-steps per slice; K = 11008 / 14336: 43 / 56, staged in chunks).  Anything else runs through
+// k_gemv_groups; both produce the same bits.  plan_slices decides (no launch, no HIP call), launch_slices launches what it decided.
 static int g_gemv_slices = 1;     // dd_set_tuning key 13
 int g_exp_temporal = 0;        // dd_tools_set_tuning key 36: slice kernels load weight tiles with the default cache policy (A/B)
-int g_exp_U9 = 4;                // dd_tools_set_tuning key 29: weight requests in flight per wave of the nine-plane qkv kernel (4 or 8; gate/up: always 4)
-int g_exp_G[4] = {0, 0, 0, 0};   // dd_set_tuning keys 17..19: workgroups per slice of the 64-row kernels (qkv, o, gate/up); 0 = default
 static int g_slices_only = 0;     // dd_lm_time_gemv: launch the streaming kernel without its finishing kernel (timing only)
 void ddk_set_gemv_slices(int on) { g_gemv_slices = on; }
 void ddk_set_slices_only(int on) { g_slices_only = on; }
-#define SLICES_UNSUPPORTED 1
-
-extern int g_seq_prog;
 // dd_tools_set_tuning key 50: the rows' rstd in a workgroup of its own behind the streaming ones (SliceArgs::rstd_wg; default 1; 0 = workgroup 0
 // does it before its own weight stream, as until round 5's last day).  Same bits either way.
 int g_rstd_wg = 1;
-static inline int rstd_blocks(const SliceArgs& sa) { return sa.rstd_wg && sa.ssq_in ? (sa.halves == 2 ? 2 : 1) : 0; }
+// dd_tools_set_tuning key 49: progressive stage-in of the operand planes (dd_gemv_slices.h PROG) in the whole-slice kernels at two and four planes
+// (default 1; 0 = the blocking stage-in of rounds 2-4).  Same bits either way.
+int g_seq_prog = 1;
+#ifdef DD_TIMING_EXPERIMENTS
+// (tools library only) QUADS: four slices added up inside a workgroup, two partial sums per tile instead of four — the sums come out in an order
+// no other pass width produces, so this is a timing experiment (DESIGN.md 3g; dd_tools_set_tuning key 53: 1 = 96 / 86 workgroups per quad for
+// qkv / gate-up (one / two tiles per wave), 2 = gate/up on 128 per quad)
+int g_seq_quads = 0;
+#endif
+
+// Every slice-kernel instantiation the library launches, once: X(name, template arguments).  A new pass width adds its rows here and its
+// branch in plan_slices.
+// k_gemv_slices<TW, NG, U, SPW, CS, CH, wf, TAG, prog>: whole slices (CH = 2: slice pairs resident together), long K in chunks of CS steps
+// (16 instead of 8 weight requests in flight per wave measured the same or slower: qkv 26.3 vs 25.4 us, gate/up 38.4 vs 38.0)
+#define SLICE_KERNELS_K(X)                       \
+  X(K_STORE_4, 1, 4, 8, 16, 16, 2, EPI_STORE)    \
+  X(K_STORE_8, 1, 8, 8, 16, 16, 1, EPI_STORE)    \
+  X(K_STORE_9, 1, 9, 8, 16, 16, 1, EPI_STORE)    \
+  X(K_QKV_2, 2, 2, 8, 16, 16, 1, EPI_QKV)        \
+  X(K_QKV_4, 2, 4, 8, 16, 16, 1, EPI_QKV)        \
+  X(K_QKV_8, 1, 8, 8, 16, 16, 1, EPI_QKV)        \
+  X(K_SILU_2, 1, 2, 8, 16, 16, 2, EPI_SILU)      \
+  X(K_SILU_4, 1, 4, 8, 16, 16, 2, EPI_SILU)      \
+  X(K_SILU_8, 1, 8, 8, 16, 16, 1, EPI_SILU)      \
+  X(K_SILU_9, 1, 9, 8, 16, 16, 1, EPI_SILU)      \
+  X(K_O_HALVES, 1, 4, 8, 16, 16, 1, EPI_RESID)   \
+  X(K_O_9, 1, 9, 8, 16, 16, 1, EPI_RESID)        \
+  X(K_DOWN43_2, 1, 2, 8, 43, 16, 1, EPI_RESID)   \
+  X(K_DOWN43_4, 1, 4, 8, 43, 16, 1, EPI_RESID)   \
+  X(K_DOWN43_8, 1, 8, 8, 43, 8, 1, EPI_RESID)    \
+  X(K_DOWN43_9, 1, 9, 8, 43, 8, 1, EPI_RESID)    \
+  X(K_DOWN56_2, 1, 2, 8, 56, 16, 1, EPI_RESID)   \
+  X(K_DOWN56_4, 1, 4, 8, 56, 16, 1, EPI_RESID)   \
+  X(K_DOWN56_8, 1, 8, 8, 56, 8, 1, EPI_RESID)    \
+  X(K_DOWN56_9, 1, 9, 8, 56, 8, 1, EPI_RESID)
+// k_gemv_slices_seq<NG, U, 16, MAXG, wf, TAG, 2>: slice PAIRS, one slice resident at a time, up to MAXG tiles per wave
+// (nine planes: four weight requests in flight per wave; with eight, three tiles per wave need 257 registers)
+#define SLICE_KERNELS_SEQ(X)          \
+  X(SEQ_QKV_8, 8, 8, 2, EPI_QKV)      \
+  X(SEQ_SILU_8, 8, 8, 3, EPI_SILU)    \
+  X(SEQ_QKV_9, 9, 4, 2, EPI_QKV)      \
+  X(SEQ_SILU_9, 9, 4, 3, EPI_SILU)
+#ifdef DD_TIMING_EXPERIMENTS
+#define SLICE_KERNELS_QUADS(X)        \
+  X(QUADS_QKV_9, 9, 4, 1, EPI_QKV)    \
+  X(QUADS_SILU_9, 9, 4, 2, EPI_SILU)
+#else
+#define SLICE_KERNELS_QUADS(X)
+#endif
+// k_gemv_slices_fp8<NG, SPW2, CH, UW, 0, XPF>: fp8 tiles, whole slices of SPW2 64-k steps.  XPF = 6 (nine planes): the operand fragments
+// through a ring, five reads ahead of their MFMAs
+#define SLICE_KERNELS_FP8(X)          \
+  X(FP8_2, 2, 8, 2, 8, 0)             \
+  X(FP8_4, 4, 8, 2, 8, 0)             \
+  X(FP8_8, 8, 8, 1, 8, 0)             \
+  X(FP8_9, 9, 8, 1, 8, 6)             \
+  X(FP8_DOWN_2, 2, 28, 1, 7, 0)
+// k_gemv_slices_fp8c<NG, SPW2, CS2, UW, 0>: fp8 tiles, K = 14336 staged in chunks of CS2 steps, one tile per wave
+#define SLICE_KERNELS_FP8C(X)         \
+  X(FP8C_4, 4, 28, 7, 7)              \
+  X(FP8C_8, 8, 28, 4, 4)              \
+  X(FP8C_9, 9, 28, 4, 4)
+enum SliceKernel {
+#define X(name, ...) name,
+  SLICE_KERNELS_K(X) SLICE_KERNELS_SEQ(X) SLICE_KERNELS_QUADS(X) SLICE_KERNELS_FP8(X) SLICE_KERNELS_FP8C(X)
+#undef X
+};
+// streaming workgroups per unit of SliceArgs::G (and per half pass)
+static int slice_wgs_per_G(int kernel) {
+  switch (kernel) {
+#define X(name, TW, NG, U, SPW, CS, CH, TAG) case name: return 8 / CH;
+    SLICE_KERNELS_K(X)
+#undef X
+#define X(name, ...) case name: return 4;
+    SLICE_KERNELS_SEQ(X)
+#undef X
+#define X(name, ...) case name: return 2;
+    SLICE_KERNELS_QUADS(X)
+#undef X
+#define X(name, NG, SPW2, CH, UW, XPF) case name: return 8 / CH;
+    SLICE_KERNELS_FP8(X)
+#undef X
+    default: return 8;    // fp8c
+  }
+}
+
+struct SlicePlan {
+  int kernel;                        // SliceKernel
+  int n_groups, G, halves;           // SliceArgs
+  int grid;                          // streaming workgroups + the rstd workgroup of each half pass
+  int fin_np, fin_tiles, fin_sets;   // k_gemv_finish4<epi, fin_tiles, planes, fin_np> on fin_sets workgroups
+};
+
+// Which slice kernel a `planes`-plane GEMV (2, 4, 8 or 9) runs, on how many workgroups, and what finishes it; false: none (k_gemv_groups).
+// n_tiles as in GemvArgs (EPI_SILU: gate/up pairs); norm_in: the operand rows carry a folded RMSNorm (GemvArgs::ssq_in).  Reads nothing but
+// its arguments and the kept switches (keys 13, 50, 53).
+static bool plan_slices(int epi, int planes, int wq, int wf, int S, int n_tiles, int half_planes, size_t part_floats, bool norm_in,
+                        SlicePlan& p) {
+  const int NG = planes;
+  const int nt = epi == EPI_SILU ? 2 * n_tiles : n_tiles;      // 16-row weight tiles
+  if (!(NG == 2 || NG == 4 || NG == 8 || NG == 9) || (NG != 9 && !g_gemv_slices)) return false;
+  if (wq == DD_WQ_MXFP4) return false;     // no slice kernels for MXFP4 tiles: k_gemv_groups (64 rows: two 32-row passes)
+  if (epi < EPI_STORE || epi > EPI_QKV || S % GEMV_WAVES || nt < 64) return false;
+  if (half_planes && (wq || !((NG == 8 && half_planes == 8) || (NG == 9 && half_planes == 7)))) return false;
+  // np = partial sums per output: 8 (single slices), 4 (slice pairs), 2 (quads); eight and nine planes always ask for room for eight
+  auto plan = [&](int kernel, int G, int np, int n_groups, int halves = 1) {
+    if (part_floats < (size_t)(NG >= 8 ? 8 : np) * nt * NG * 128) return false;
+    p.kernel = kernel, p.n_groups = n_groups, p.G = G, p.halves = halves;
+    p.grid = halves * (slice_wgs_per_G(kernel) * G + (g_rstd_wg && norm_in ? 1 : 0));
+    p.fin_np = np, p.fin_tiles = epi == EPI_SILU ? 2 : 1, p.fin_sets = n_tiles;
+    return true;
+  };
+  if (wq) {
+    // fp8 tiles (weight_format 1): K = 4096 (8 steps of 64 k per slice: slice pairs up to four planes, single slices at eight and nine —
+    // 128 / 144 KiB of operands) and K = 14336 (28 steps; Mistral-7B's down_proj): two planes hold a whole slice in LDS, more stage it in
+    // chunks, one tile per wave; other shapes stay on the wave-split kernels — the same bits either way
+    const int spw2 = S / 16, G1 = (nt + 7) / 8;            // G1: one tile per wave
+    if (S % 16 || !(spw2 == 8 || (spw2 == 28 && (NG < 9 || epi == EPI_RESID)))) return false;
+    // G <= 32 / 64: one round of workgroups (one per CU at 64-144 KiB of operands)
+    if (spw2 == 28) return NG == 2 ? plan(FP8_DOWN_2, G1 < 32 ? G1 : 32, 8, nt) : plan(NG == 4 ? FP8C_4 : (NG == 8 ? FP8C_8 : FP8C_9), G1, 8, nt);
+    if (NG <= 4) return plan(NG == 2 ? FP8_2 : FP8_4, G1 < 64 ? G1 : 64, 4, nt);
+    return plan(NG == 8 ? FP8_8 : FP8_9, G1 < 32 ? G1 : 32, 8, nt);
+  }
+  const int spw = S / GEMV_WAVES;
+  if (!(spw == 16 || spw == 43 || spw == 56)) return false;
+  if (epi == EPI_STORE) {
+    // lm_head (K = 4096): the wave-split kernel streams it at 2.8 TB/s with four planes (operand reads from L2); the slice kernels
+    // with the plain-store finish: 32 rows as slice pairs, 64 / 72 rows as single slices, 16 rows stay on the wave-split kernel
+    if (spw != 16 || NG < 4) return false;
+    if (NG == 4) return plan(K_STORE_4, 64, 4, nt);
+    return plan(NG == 8 ? K_STORE_8 : K_STORE_9, (nt + 31) / 32, 8, nt);
+  }
+  if (epi == EPI_RESID) {
+    if (spw == 16) {
+      // K = 4096 (o_proj) at two and four planes: the wave-split kernel in one launch is as fast as slices + finish (13.5 vs 14.2 us at
+      // four planes, 10.3 vs 11.2 at two: 33 MB of weights do not amortise a second launch)
+      if (NG <= 4) return false;
+      // 64 rows: two half passes of four planes over the same tiles, paired on one XCD so that the second reads the tiles from L2
+      // (dd_gemv_slices.h `halves`): 10.4 vs 13.5 us for the eight-plane kernel (the wide matrices lose with it)
+      if (NG == 8) return plan(K_O_HALVES, (nt + 15) / 16, 8, nt, 2);
+      // 72 rows: two tiles per wave on 8 * 16 = 128 workgroups at N = 4096: alone 14.7 us against 11.2 with one tile per wave on 256, but
+      // inside the step, beside the other branch's kernels, the half-chip grid wins (20.9 vs 21.4 ms per 32-lane step)
+      return plan(K_O_9, (nt + 15) / 16, 8, nt);
+    }
+    // long K (down): one tile per wave, the slice staged in chunks of 16 steps (eight / nine planes: 8); gains 30 % on the wave-split kernel
+    static const int k43[] = {K_DOWN43_2, K_DOWN43_4, K_DOWN43_8, K_DOWN43_9}, k56[] = {K_DOWN56_2, K_DOWN56_4, K_DOWN56_8, K_DOWN56_9};
+    const int i = NG == 2 ? 0 : (NG == 4 ? 1 : (NG == 8 ? 2 : 3));
+    return plan(spw == 43 ? k43[i] : k56[i], (nt + 7) / 8, 8, nt);
+  }
+  if (spw != 16) return false;
+  if (epi == EPI_QKV) {
+    if (NG <= 4) {     // tile pairs; two pairs per wave when there are enough
+      const int ng = nt / 2;
+      return !(nt & 1) && plan(NG == 2 ? K_QKV_2 : K_QKV_4, ng >= 256 ? (ng + 15) / 16 : (ng + 7) / 8, 8, ng);
+    }
+    // 64 / 72 rows: 8 / 9 operand planes fill the LDS with one slice (16 steps x 8 KiB = 128 KiB at K = 4096), one workgroup per CU;
+    // tools/gemv_lab: qkv 28 us, o 10.7, gate/up 45, down 21 — 1.25 x the 32-row kernels for twice the rows.
+    // Slice pairs, one slice resident at a time (see gate/up below), two tiles per wave in one round of 4 * G <= 256 workgroups (32 lanes:
+    // 32.6 -> 31.6 ms per group step for the three matrices' choices together); other tile counts: single slices (eight planes only)
+    const bool pairs = nt % 16 == 0 && nt / 16 * 4 <= 256;
+#ifdef DD_TIMING_EXPERIMENTS
+    if (NG == 9 && pairs && g_seq_quads && !wf && nt / 8 <= 128) return plan(QUADS_QKV_9, nt / 8, 2, nt);     // one tile per wave, 2 * G workgroups
+#endif
+    if (pairs) return plan(NG == 8 ? SEQ_QKV_8 : SEQ_QKV_9, nt / 16, 4, nt);
+    return NG == 8 && plan(K_QKV_8, (nt + 31) / 32, 8, nt);
+  }
+  // EPI_SILU
+  if (NG <= 4) return plan(NG == 2 ? K_SILU_2 : K_SILU_4, 64, 4, nt);      // slice pairs, one workgroup per CU
+  // slice pairs, one slice resident at a time: half the partial sums.  Three tiles per wave, as evenly as the tile count allows, in ONE
+  // round of workgroups (LLaVA-7B: 58 per pair = 232): 27.25 vs 27.75 ms per 32-lane step; 64 per pair (2.7 tiles per wave: uneven)
+  // 28.6, 86 (two tiles, 1.3 rounds) 29.1.  More tiles than that (Mistral-7B: 1792): single slices, tiles walked per wave
+  if (4 * ((nt + 23) / 24) > 256) return NG == 8 ? plan(K_SILU_8, (nt + 42) / 43, 8, nt) : plan(K_SILU_9, 32, 8, nt);
+#ifdef DD_TIMING_EXPERIMENTS
+  if (NG == 9 && g_seq_quads && !wf) {
+    const int G = g_seq_quads == 2 ? 128 : (nt + 15) / 16;    // two tiles per wave
+    if ((nt + 8 * G - 1) / (8 * G) <= 2) return plan(QUADS_SILU_9, G, 2, nt);
+  }
+#endif
+  return plan(NG == 8 ? SEQ_SILU_8 : SEQ_SILU_9, (nt + 23) / 24, 4, nt);
+}
+
+// One launcher per kernel family: notes the kernel's name as a trace prints it, and launches it unless sa is null (ddk_gemv_plan).
+// The dynamic-LDS attribute is set once per instantiation.
 template <int TW, int NG, int U, int SPW, int CS, int CH, int TAG>
-static int launch_slices_k(const SliceArgs& sa, int wf, hipStream_t st) {
+static int launch_slices_k(const SliceArgs* sa, int wf, int grid, hipStream_t st) {
   constexpr size_t smem = (size_t)CH * (SPW < CS ? SPW : CS) * NG * 1024;
   // progressive stage-in (dd_gemv_slices.h PROG): whole-slice kernels with at least two ring blocks per tile group
   // Measured (profiles/r05_progressive_stage_in.log): it pays at two and four planes (16 / 32 rows: gate/up 33.7 -> 32.7 / 36.4 -> 35.0 us) and
   // costs at eight and nine (the per-block barriers of the first tile group: 64-lane step 36.4 -> 37.7 ms) — so only NG <= 4 takes it.
   constexpr int PROG_OK = (NG <= 4 && SPW <= CS && (CH * SPW) / (SPW < U ? SPW : U) >= 2) ? 1 : 0;
+  const int prog = g_seq_prog && PROG_OK;
+  NOTE_KERNEL("k_gemv_slices<%d, %d, %d, %d, %d, %d, %d, %d, %d>", TW, NG, U, SPW, CS, CH, wf ? 1 : 0, TAG, prog);
+  if (!sa) return DD_OK;
   static bool attr = false;
   if (!attr) {
     DD_HIP(hipFuncSetAttribute((const void*)k_gemv_slices<TW, NG, U, SPW, CS, CH, 0, TAG, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
@@ -1125,367 +1210,146 @@ static int launch_slices_k(const SliceArgs& sa, int wf, hipStream_t st) {
     DD_HIP(hipFuncSetAttribute((const void*)k_gemv_slices<TW, NG, U, SPW, CS, CH, 1, TAG, PROG_OK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     attr = true;
   }
-  const int grid = (sa.halves == 2 ? 2 : 1) * (8 / CH) * sa.G + rstd_blocks(sa);
-  const int prog = g_seq_prog && PROG_OK;
-  NOTE_KERNEL("k_gemv_slices<%d, %d, %d, %d, %d, %d, %d, %d, %d>", TW, NG, U, SPW, CS, CH, wf ? 1 : 0, TAG, prog);
   if (prog) {
-    if (wf) k_gemv_slices<TW, NG, U, SPW, CS, CH, 1, TAG, PROG_OK><<<grid, GEMV_THREADS, smem, st>>>(sa);
-    else k_gemv_slices<TW, NG, U, SPW, CS, CH, 0, TAG, PROG_OK><<<grid, GEMV_THREADS, smem, st>>>(sa);
+    if (wf) k_gemv_slices<TW, NG, U, SPW, CS, CH, 1, TAG, PROG_OK><<<grid, GEMV_THREADS, smem, st>>>(*sa);
+    else k_gemv_slices<TW, NG, U, SPW, CS, CH, 0, TAG, PROG_OK><<<grid, GEMV_THREADS, smem, st>>>(*sa);
   } else {
-    if (wf) k_gemv_slices<TW, NG, U, SPW, CS, CH, 1, TAG, 0><<<grid, GEMV_THREADS, smem, st>>>(sa);
-    else k_gemv_slices<TW, NG, U, SPW, CS, CH, 0, TAG, 0><<<grid, GEMV_THREADS, smem, st>>>(sa);
+    if (wf) k_gemv_slices<TW, NG, U, SPW, CS, CH, 1, TAG, 0><<<grid, GEMV_THREADS, smem, st>>>(*sa);
+    else k_gemv_slices<TW, NG, U, SPW, CS, CH, 0, TAG, 0><<<grid, GEMV_THREADS, smem, st>>>(*sa);
   }
   return DD_OK;
 }
-// (16 instead of 8 weight requests in flight per wave measured the same or slower: qkv 26.3 vs 25.4 us, gate/up 38.4 vs 38.0)
-// dd_tools_set_tuning key 49: progressive stage-in of the operand planes (dd_gemv_slices.h PROG) in the whole-slice kernels at two and four planes
-// (default 1; 0 = the blocking stage-in of rounds 2-4).  Same bits either way.
-int g_seq_prog = 1;
 template <int NG, int U, int MAXG, int TAG>
-static int launch_slices_seq(const SliceArgs& sa, int wf, hipStream_t st) {
+static int launch_slices_seq(const SliceArgs* sa, int wf, int grid, hipStream_t st) {
   constexpr size_t smem = (size_t)16 * NG * 1024;
+  NOTE_KERNEL("k_gemv_slices_seq<%d, %d, 16, %d, %d, %d, 2>", NG, U, MAXG, wf ? 1 : 0, TAG);   // (the last argument: slices per workgroup, pairs)
+  if (!sa) return DD_OK;
   static bool attr = false;
   if (!attr) {
     DD_HIP(hipFuncSetAttribute((const void*)k_gemv_slices_seq<NG, U, 16, MAXG, 0, TAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     DD_HIP(hipFuncSetAttribute((const void*)k_gemv_slices_seq<NG, U, 16, MAXG, 1, TAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     attr = true;
   }
-  NOTE_KERNEL("k_gemv_slices_seq<%d, %d, 16, %d, %d, %d, 2>", NG, U, MAXG, wf ? 1 : 0, TAG);   // (the last argument: slices per workgroup, pairs)
-  if (wf) k_gemv_slices_seq<NG, U, 16, MAXG, 1, TAG><<<4 * sa.G + rstd_blocks(sa), GEMV_THREADS, smem, st>>>(sa);
-  else k_gemv_slices_seq<NG, U, 16, MAXG, 0, TAG><<<4 * sa.G + rstd_blocks(sa), GEMV_THREADS, smem, st>>>(sa);
+  if (wf) k_gemv_slices_seq<NG, U, 16, MAXG, 1, TAG><<<grid, GEMV_THREADS, smem, st>>>(*sa);
+  else k_gemv_slices_seq<NG, U, 16, MAXG, 0, TAG><<<grid, GEMV_THREADS, smem, st>>>(*sa);
   return DD_OK;
 }
-
 #ifdef DD_TIMING_EXPERIMENTS
-// (tools library only) QUADS: four slices added up inside a workgroup, two partial sums per tile instead of four — the sums come out in an order
-// no other pass width produces, so this is a timing experiment (DESIGN.md 3g; dd_tools_set_tuning key 53: 1 = 96 / 86 workgroups per quad for
-// qkv / gate-up (one / two tiles per wave), 2 = gate/up on 128 per quad)
-int g_seq_quads = 0;
 template <int NG, int U, int MAXG, int TAG>
-static int launch_slices_seq_quads(const SliceArgs& sa, int wf, hipStream_t st) {
+static int launch_slices_seq_quads(const SliceArgs* sa, int wf, int grid, hipStream_t st) {
   constexpr size_t smem = (size_t)16 * NG * 1024;
+  NOTE_KERNEL("k_gemv_slices_seq<%d, %d, 16, %d, 0, %d, 4>", NG, U, MAXG, TAG);
+  if (!sa) return DD_OK;
+  DD_REQUIRE(!wf, "quads: bf16 tiles only");
   static bool attr = false;
   if (!attr) {
     DD_HIP(hipFuncSetAttribute((const void*)k_gemv_slices_seq<NG, U, 16, MAXG, 0, TAG, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     attr = true;
   }
-  NOTE_KERNEL("k_gemv_slices_seq<%d, %d, 16, %d, 0, %d, 4>", NG, U, MAXG, TAG);
-  DD_REQUIRE(!wf, "quads: bf16 tiles only");
-  k_gemv_slices_seq<NG, U, 16, MAXG, 0, TAG, 4><<<2 * sa.G + rstd_blocks(sa), GEMV_THREADS, smem, st>>>(sa);
+  k_gemv_slices_seq<NG, U, 16, MAXG, 0, TAG, 4><<<grid, GEMV_THREADS, smem, st>>>(*sa);
   return DD_OK;
 }
 #endif
-int g_finish4 = 15;   // dd_tools_set_tuning key 24: the four-columns-per-thread finishing kernel per epilogue (bit = EPI_*; 0: k_gemv_finish, same bits)
-template <int EPI, int TILES, int NG, int NP>
-static void launch_finish(const GemvArgs& a, int n_sets, hipStream_t st) {
-  if (g_slices_only) return;
-  if ((g_finish4 & (1 << EPI)) || a.wq == DD_WQ_FP8) k_gemv_finish4<EPI, TILES, NG, NP><<<n_sets, 32 * NG, 0, st>>>(a, a.part, a.part + a.part_floats, n_sets);
-  else k_gemv_finish<EPI, TILES, NG, NP><<<n_sets, 128 * NG, 0, st>>>(a, a.part, a.part + a.part_floats, n_sets);
-}
-template <int NG, int SPW2, int CH, int UW>
-static int launch_slices_fp8(const SliceArgs& sa, hipStream_t st) {
+template <int NG, int SPW2, int CH, int UW, int XPF>
+static int launch_slices_fp8(const SliceArgs* sa, int grid, hipStream_t st) {
   constexpr size_t smem = (size_t)CH * 2 * SPW2 * NG * 1024;
+  NOTE_KERNEL("k_gemv_slices_fp8<%d, %d, %d, %d, 0, %d>", NG, SPW2, CH, UW, XPF);
+  if (!sa) return DD_OK;
   static bool attr = false;
   if (!attr) {
-    DD_HIP(hipFuncSetAttribute((const void*)k_gemv_slices_fp8<NG, SPW2, CH, UW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    DD_HIP(hipFuncSetAttribute((const void*)k_gemv_slices_fp8<NG, SPW2, CH, UW, 0, XPF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     attr = true;
   }
-  NOTE_KERNEL("k_gemv_slices_fp8<%d, %d, %d, %d, 0, 0>", NG, SPW2, CH, UW);
-  k_gemv_slices_fp8<NG, SPW2, CH, UW><<<(8 / CH) * sa.G + rstd_blocks(sa), GEMV_THREADS, smem, st>>>(sa);
+  k_gemv_slices_fp8<NG, SPW2, CH, UW, 0, XPF><<<grid, GEMV_THREADS, smem, st>>>(*sa);
   return DD_OK;
 }
-int g_fp8_xpf = 1;       // dd_tools_set_tuning key 52: the nine-plane fp8 kernel's operand fragments through a ring, five reads ahead of their MFMAs
-                         // (default; 0: requested where the compiler puts them — one MFMA ahead; same bits)
 template <int NG, int SPW2, int CS2, int UW>
-static int launch_slices_fp8c(const SliceArgs& sa, hipStream_t st) {
+static int launch_slices_fp8c(const SliceArgs* sa, int grid, hipStream_t st) {
   constexpr size_t smem = (size_t)2 * CS2 * NG * 1024;
+  NOTE_KERNEL("k_gemv_slices_fp8c<%d, %d, %d, %d, 0>", NG, SPW2, CS2, UW);
+  if (!sa) return DD_OK;
   static bool attr = false;
   if (!attr) {
     DD_HIP(hipFuncSetAttribute((const void*)k_gemv_slices_fp8c<NG, SPW2, CS2, UW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     attr = true;
   }
-  NOTE_KERNEL("k_gemv_slices_fp8c<%d, %d, %d, %d, 0>", NG, SPW2, CS2, UW);
-  k_gemv_slices_fp8c<NG, SPW2, CS2, UW><<<8 * sa.G + rstd_blocks(sa), GEMV_THREADS, smem, st>>>(sa);
+  k_gemv_slices_fp8c<NG, SPW2, CS2, UW><<<grid, GEMV_THREADS, smem, st>>>(*sa);
   return DD_OK;
 }
-template <int EPI, int TILES, int NG>
-static void finish_fp8(const GemvArgs& a, int n_sets, int ch, hipStream_t st) {
-  if (ch == 2) launch_finish<EPI, TILES, NG, 4>(a, n_sets, st);
-  else launch_finish<EPI, TILES, NG, 8>(a, n_sets, st);
-}
-// fp8 tiles (weight_format 1): K = 4096 (8 steps of 64 k per slice: slice pairs up to four planes, single slices at eight) and,
-// for two planes, K = 14336 (28 steps); other shapes stay on the wave-split kernels — the same bits either way
-template <int NG>
-static int try_slices_fp8(int epi, const GemvArgs& a, hipStream_t st) {
-  const int nt = epi == EPI_SILU ? 2 * a.n_tiles : a.n_tiles;
-  const int spw2 = a.S / 16;
-  if (a.S % 16 || nt < 64 || !(spw2 == 8 || spw2 == 28)) return SLICES_UNSUPPORTED;
-  const int ch = (spw2 == 8 && NG <= 4) ? 2 : 1;
-  if (a.part_floats < (size_t)(8 / ch) * nt * NG * 128) return SLICES_UNSUPPORTED;
-  SliceArgs sa;
-  sa.W = a.W, sa.xop = a.xop, sa.part = a.part, sa.S = a.S, sa.halves = 1, sa.n_groups = nt;
-  sa.ssq_in = a.ssq_in, sa.ssq_n = a.ssq_n, sa.ssq_ld = a.ssq_ld, sa.inv_k = a.inv_k, sa.eps = a.eps;
-  sa.rstd_out = a.part + a.part_floats, sa.temporal = g_exp_temporal, sa.rstd_wg = g_rstd_wg;
-  const int per_set = 256 / (8 / ch);                  // one round of workgroups (one per CU at 64-128 KiB of operands)
-  sa.G = (nt + 7) / 8 < per_set ? (nt + 7) / 8 : per_set;
-  if (spw2 == 28) {
-    // K = 14336 (down_proj of Mistral-7B): two planes hold a whole slice in LDS; four / eight planes stage it in chunks, one tile per wave
-    if constexpr (NG == 2) {
-      RC_(launch_slices_fp8<2, 28, 1, 7>(sa, st));
-    } else {
-      sa.G = (nt + 7) / 8;
-      if constexpr (NG == 4) RC_(launch_slices_fp8c<4, 28, 7, 7>(sa, st));
-      else RC_(launch_slices_fp8c<8, 28, 4, 4>(sa, st));
-    }
-  } else if constexpr (NG <= 4) {
-    RC_(launch_slices_fp8<NG, 8, 2, 8>(sa, st));
-  } else {
-    RC_(launch_slices_fp8<NG, 8, 1, 8>(sa, st));
+static int launch_slice_kernel(const SlicePlan& p, const SliceArgs* sa, int wf, hipStream_t st) {
+  switch (p.kernel) {
+#define X(id, ...) case id: return launch_slices_k<__VA_ARGS__>(sa, wf, p.grid, st);
+    SLICE_KERNELS_K(X)
+#undef X
+#define X(id, ...) case id: return launch_slices_seq<__VA_ARGS__>(sa, wf, p.grid, st);
+    SLICE_KERNELS_SEQ(X)
+#undef X
+#define X(id, ...) case id: return launch_slices_seq_quads<__VA_ARGS__>(sa, wf, p.grid, st);
+    SLICE_KERNELS_QUADS(X)
+#undef X
+#define X(id, ...) case id: return launch_slices_fp8<__VA_ARGS__>(sa, p.grid, st);
+    SLICE_KERNELS_FP8(X)
+#undef X
+#define X(id, ...) case id: return launch_slices_fp8c<__VA_ARGS__>(sa, p.grid, st);
+    SLICE_KERNELS_FP8C(X)
+#undef X
   }
-  switch (epi) {
-    case EPI_STORE: finish_fp8<EPI_STORE, 1, NG>(a, nt, ch, st); break;
-    case EPI_RESID: finish_fp8<EPI_RESID, 1, NG>(a, nt, ch, st); break;
-    case EPI_SILU: finish_fp8<EPI_SILU, 2, NG>(a, a.n_tiles, ch, st); break;
-    default: finish_fp8<EPI_QKV, 1, NG>(a, nt, ch, st); break;
-  }
-  return DD_OK;
+  DD_REQUIRE(false, "gemv_slices: unknown kernel %d", p.kernel);
 }
 
-template <int NG>
-static int try_slices(int epi, const GemvArgs& a, hipStream_t st) {
-  if (a.wq == DD_WQ_MXFP4) return SLICES_UNSUPPORTED;     // no slice kernels for MXFP4 tiles: k_gemv_groups (64 rows: two 32-row passes)
-  if (a.wq) return try_slices_fp8<NG>(epi, a, st);
-  const int spw = a.S / GEMV_WAVES;
-  const int nt = epi == EPI_SILU ? 2 * a.n_tiles : a.n_tiles;      // 16-row weight tiles
-  if (!(spw == 16 || spw == 43 || spw == 56) || nt < 64) return SLICES_UNSUPPORTED;
-  SliceArgs sa;
-  sa.W = a.W, sa.xop = a.xop, sa.part = a.part, sa.S = a.S, sa.halves = 1;
-  sa.ssq_in = a.ssq_in, sa.ssq_n = a.ssq_n, sa.ssq_ld = a.ssq_ld, sa.inv_k = a.inv_k, sa.eps = a.eps;
-  sa.rstd_out = a.part + a.part_floats, sa.temporal = g_exp_temporal, sa.rstd_wg = g_rstd_wg;                              // 32 floats behind the partial sums
-  const size_t need8 = (size_t)8 * nt * NG * 128, need4 = need8 / 2;
-  if (epi == EPI_STORE) {
-    // lm_head (K = 4096): the wave-split kernel streams it at 2.8 TB/s with four planes (operand reads from L2); the slice kernels
-    // with the plain-store finish: 32 rows as slice pairs, 64 rows as single slices, 16 rows stay on the wave-split kernel
-    if (spw != 16 || NG < 4) return SLICES_UNSUPPORTED;
-    sa.n_groups = nt;
-    if constexpr (NG == 8) {
-      if (a.part_floats < need8) return SLICES_UNSUPPORTED;
-      sa.G = (nt + 31) / 32;
-      RC_(launch_slices_k<1, 8, 8, 16, 16, 1, EPI_STORE>(sa, a.wf, st));
-      launch_finish<EPI_STORE, 1, 8, 8>(a, nt, st);
-    } else {
-      if (a.part_floats < need4) return SLICES_UNSUPPORTED;
-      sa.G = 64;
-      RC_(launch_slices_k<1, NG, 8, 16, 16, 2, EPI_STORE>(sa, a.wf, st));
-      launch_finish<EPI_STORE, 1, NG, 4>(a, nt, st);
-    }
-    return DD_OK;
+// The finishing kernel of a plan.  Up to four planes every epilogue exists with 4 and 8 partial sums (fp8: slice pairs at K = 4096, single
+// slices at K = 14336); at eight and nine planes only the slice-pair kernels (qkv, gate/up) leave fewer than 8.
+template <int EPI, int TILES>
+static int launch_finish(const GemvArgs& a, const SlicePlan& p, hipStream_t st) {
+  constexpr bool PAIRS = EPI == EPI_QKV || EPI == EPI_SILU;
+  const float* rstd = a.part + a.part_floats;
+#define FIN(NG_, NP_)                                                                                  \
+  if (a.n_groups == NG_ && p.fin_np == NP_) {                                                          \
+    k_gemv_finish4<EPI, TILES, NG_, NP_><<<p.fin_sets, 32 * NG_, 0, st>>>(a, a.part, rstd, p.fin_sets); \
+    return DD_OK;                                                                                      \
   }
-  if constexpr (NG == 8) {
-    // 64 rows: 8 operand planes fill the LDS with one slice (16 steps x 8 KiB = 128 KiB at K = 4096; long K in chunks of 8
-    // steps), one tile per wave group; tools/gemv_lab: qkv 28 us, o 10.7, gate/up 45, down 21 — 1.25 x the 32-row kernels for
-    // twice the rows
-    if (a.part_floats < need8) return SLICES_UNSUPPORTED;
-    sa.n_groups = nt;
-    if (epi == EPI_QKV) {
-      if (spw != 16) return SLICES_UNSUPPORTED;
-      // workgroups per slice: one round of 8 * G <= 256 workgroups (one per CU: 128 KiB of operands each) measured best inside
-      // the sweep (32 lanes: 32.6 -> 31.6 ms per group step for the three choices together)
-      if (g_exp_G[0] >= 0 && (nt % 16) == 0 && nt / 16 * 4 <= 256) {
-        // slice pairs, one slice resident at a time (see gate/up below): two tiles per wave; tuning key 17 < 0: single slices (A/B)
-        sa.G = g_exp_G[0] ? g_exp_G[0] : nt / 16;
-        DD_REQUIRE((nt + 8 * sa.G - 1) / (8 * sa.G) <= 2, "gemv_slices_seq: %d tiles over %d workgroups per pair", nt, sa.G);
-        RC_(launch_slices_seq<8, 8, 2, EPI_QKV>(sa, a.wf, st));
-        launch_finish<EPI_QKV, 1, 8, 4>(a, nt, st);
-      } else {
-        sa.G = g_exp_G[0] > 0 ? g_exp_G[0] : (nt + 31) / 32;
-        RC_(launch_slices_k<1, 8, 8, 16, 16, 1, EPI_QKV>(sa, a.wf, st));
-        launch_finish<EPI_QKV, 1, 8, 8>(a, nt, st);
-      }
-    } else if (epi == EPI_RESID) {
-      sa.G = (nt + 7) / 8;
-      if (spw == 16 && g_exp_G[1] < 0) {                       // tuning key 18 < 0: the eight-plane kernel (A/B)
-        sa.G = (nt + 15) / 16;
-        RC_(launch_slices_k<1, 8, 8, 16, 16, 1, EPI_RESID>(sa, a.wf, st));
-      } else if (spw == 16) {
-        // o_proj (33 MB): two half passes of four planes over the same tiles, paired on one XCD so that the second reads the
-        // tiles from L2 (dd_gemv_slices.h `halves`): 10.4 vs 13.5 us for the eight-plane kernel (the wide matrices lose with it)
-        sa.G = g_exp_G[1] ? g_exp_G[1] : (nt + 15) / 16;
-        sa.halves = 2;
-        RC_(launch_slices_k<1, 4, 8, 16, 16, 1, EPI_RESID>(sa, a.wf, st));
-        sa.halves = 1;
-      }
-      else if (spw == 43) RC_(launch_slices_k<1, 8, 8, 43, 8, 1, EPI_RESID>(sa, a.wf, st));
-      else RC_(launch_slices_k<1, 8, 8, 56, 8, 1, EPI_RESID>(sa, a.wf, st));
-      launch_finish<EPI_RESID, 1, 8, 8>(a, nt, st);
-    } else {
-      if (spw != 16) return SLICES_UNSUPPORTED;
-      if (g_exp_G[2] >= 0 && 4 * ((nt + 23) / 24) <= 256) {
-        // slice pairs, one slice resident at a time: half the partial sums.  Three tiles per wave, as evenly as the tile count
-        // allows, in ONE round of workgroups (LLaVA-7B: 58 per pair = 232): 27.25 vs 27.75 ms per 32-lane step; 64 per pair
-        // (2.7 tiles per wave: uneven) 28.6, 86 (two tiles, 1.3 rounds) 29.1.  Tuning key 19 < 0: single slices (A/B)
-        sa.G = g_exp_G[2] ? g_exp_G[2] : (nt + 23) / 24;
-        DD_REQUIRE((nt + 8 * sa.G - 1) / (8 * sa.G) <= 3, "gemv_slices_seq: %d tiles over %d workgroups per pair", nt, sa.G);
-        RC_(launch_slices_seq<8, 8, 3, EPI_SILU>(sa, a.wf, st));
-        launch_finish<EPI_SILU, 2, 8, 4>(a, a.n_tiles, st);
-      } else {
-        sa.G = g_exp_G[2] > 0 ? g_exp_G[2] : (nt + 42) / 43;
-        RC_(launch_slices_k<1, 8, 8, 16, 16, 1, EPI_SILU>(sa, a.wf, st));
-        launch_finish<EPI_SILU, 2, 8, 8>(a, a.n_tiles, st);
-      }
-    }
-    return DD_OK;
-  } else if (epi == EPI_QKV) {
-    if (spw != 16 || (nt & 1) || a.part_floats < need8) return SLICES_UNSUPPORTED;
-    sa.n_groups = nt / 2;
-    sa.G = sa.n_groups >= 256 ? (sa.n_groups + 15) / 16 : (sa.n_groups + 7) / 8;     // two tile pairs per wave when there are enough
-    RC_(launch_slices_k<2, NG, 8, 16, 16, 1, EPI_QKV>(sa, a.wf, st));
-    launch_finish<EPI_QKV, 1, NG, 8>(a, nt, st);
-  } else if (epi == EPI_RESID) {
-    // K = 4096 (o_proj): the wave-split kernel in one launch is as fast as slices + finish (13.5 vs 14.2 us at four planes,
-    // 10.3 vs 11.2 at two: 33 MB of weights do not amortise a second launch); the long-K matrix (down) gains 30 %
-    if (a.part_floats < need8 || spw == 16) return SLICES_UNSUPPORTED;
-    sa.n_groups = nt;
-    sa.G = (nt + 7) / 8;                                             // one tile per wave
-    if (spw == 16) RC_(launch_slices_k<1, NG, 8, 16, 16, 1, EPI_RESID>(sa, a.wf, st));
-    else if (spw == 43) RC_(launch_slices_k<1, NG, 8, 43, 16, 1, EPI_RESID>(sa, a.wf, st));
-    else RC_(launch_slices_k<1, NG, 8, 56, 16, 1, EPI_RESID>(sa, a.wf, st));
-    launch_finish<EPI_RESID, 1, NG, 8>(a, nt, st);
-  } else {  // EPI_SILU: slice pairs, one workgroup per CU
-    if (spw != 16 || a.part_floats < need4) return SLICES_UNSUPPORTED;
-    sa.n_groups = nt;
-    sa.G = 64;
-    RC_(launch_slices_k<1, NG, 8, 16, 16, 2, EPI_SILU>(sa, a.wf, st));
-    launch_finish<EPI_SILU, 2, NG, 4>(a, a.n_tiles, st);
+  FIN(2, 4) FIN(2, 8) FIN(4, 4) FIN(4, 8) FIN(8, 8) FIN(9, 8)
+  if constexpr (PAIRS) {
+    FIN(8, 4) FIN(9, 4)
+#ifdef DD_TIMING_EXPERIMENTS
+    FIN(9, 2)
+#endif
   }
-  return DD_OK;
+#undef FIN
+  DD_REQUIRE(false, "gemv_slices: no finishing kernel for epilogue %d, %d planes, %d partial sums", EPI, a.n_groups, p.fin_np);
 }
 
-// Nine operand planes (72 rows): the members of eight sequences + ONE plane of un-masked rows that ride along (dd_engine.hip,
-// "rider": the base rows of the partner group's next pass, so that a group step needs no sweep of its own for them).  The 64-row
-// kernels with one more plane: a slice of K = 4096 is 144 KiB of LDS, one workgroup per CU as there; bf16 / fp16 tiles only, the
-// 7B families' shapes only (the engine does not plan riders otherwise).
-// (fp8 tiles: K = 4096 — 144 KiB of operands per slice, single slices — and K = 14336 in chunks; Mistral-7B's shapes, config 5)
-static int try_slices9_fp8(int epi, const GemvArgs& a, hipStream_t st) {
-  const int nt = epi == EPI_SILU ? 2 * a.n_tiles : a.n_tiles;
-  const int spw2 = a.S / 16;
-  if (a.S % 16 || nt < 64 || !(spw2 == 8 || (spw2 == 28 && epi == EPI_RESID))) return SLICES_UNSUPPORTED;
-  if (a.part_floats < (size_t)8 * nt * 9 * 128) return SLICES_UNSUPPORTED;
+// the streaming kernel of a plan, then its finishing kernel
+static int launch_slices(int epi, const GemvArgs& a, const SlicePlan& p, hipStream_t st) {
   SliceArgs sa;
-  sa.W = a.W, sa.xop = a.xop, sa.part = a.part, sa.S = a.S, sa.halves = 1, sa.n_groups = nt;
+  sa.W = a.W, sa.xop = a.xop, sa.part = a.part, sa.S = a.S;
+  sa.n_groups = p.n_groups, sa.G = p.G, sa.halves = p.halves;
   sa.ssq_in = a.ssq_in, sa.ssq_n = a.ssq_n, sa.ssq_ld = a.ssq_ld, sa.inv_k = a.inv_k, sa.eps = a.eps;
-  sa.rstd_out = a.part + a.part_floats, sa.temporal = g_exp_temporal, sa.rstd_wg = g_rstd_wg;
-  if (spw2 == 28) {
-    sa.G = (nt + 7) / 8;
-    RC_(launch_slices_fp8c<9, 28, 4, 4>(sa, st));
-  } else {
-    sa.G = (nt + 7) / 8 < 32 ? (nt + 7) / 8 : 32;        // one round of workgroups (one per CU: 144 KiB of operands each)
-    if (g_fp8_xpf) {
-      constexpr size_t smem = (size_t)2 * 8 * 9 * 1024;
-      static bool attr = false;
-      if (!attr) {
-        DD_HIP(hipFuncSetAttribute((const void*)k_gemv_slices_fp8<9, 8, 1, 8, 0, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr = true;
-      }
-      NOTE_KERNEL("k_gemv_slices_fp8<9, 8, 1, 8, 0, 6>");
-      k_gemv_slices_fp8<9, 8, 1, 8, 0, 6><<<8 * sa.G + rstd_blocks(sa), GEMV_THREADS, smem, st>>>(sa);
-    } else
-    RC_(launch_slices_fp8<9, 8, 1, 8>(sa, st));
-  }
+  sa.rstd_out = a.part + a.part_floats;                        // 8 * planes floats behind the partial sums
+  sa.temporal = g_exp_temporal, sa.rstd_wg = g_rstd_wg;
+  RC_(launch_slice_kernel(p, &sa, a.wf, st));
+  if (g_slices_only) return DD_OK;
   switch (epi) {
-    case EPI_STORE: launch_finish<EPI_STORE, 1, 9, 8>(a, nt, st); break;
-    case EPI_RESID: launch_finish<EPI_RESID, 1, 9, 8>(a, nt, st); break;
-    case EPI_SILU: launch_finish<EPI_SILU, 2, 9, 8>(a, a.n_tiles, st); break;
-    default: launch_finish<EPI_QKV, 1, 9, 8>(a, nt, st); break;
+    case EPI_STORE: return launch_finish<EPI_STORE, 1>(a, p, st);
+    case EPI_RESID: return launch_finish<EPI_RESID, 1>(a, p, st);
+    case EPI_SILU: return launch_finish<EPI_SILU, 2>(a, p, st);
+    default: return launch_finish<EPI_QKV, 1>(a, p, st);
   }
-  return DD_OK;
 }
-static int try_slices9(int epi, const GemvArgs& a, hipStream_t st) {
-  if (a.wq == DD_WQ_MXFP4) return SLICES_UNSUPPORTED;
-  if (a.wq) return try_slices9_fp8(epi, a, st);
-  const int spw = a.S / GEMV_WAVES;
-  const int nt = epi == EPI_SILU ? 2 * a.n_tiles : a.n_tiles;
-  if (!(spw == 16 || spw == 43 || spw == 56) || nt < 64) return SLICES_UNSUPPORTED;
-  SliceArgs sa;
-  sa.W = a.W, sa.xop = a.xop, sa.part = a.part, sa.S = a.S, sa.halves = 1;
-  sa.ssq_in = a.ssq_in, sa.ssq_n = a.ssq_n, sa.ssq_ld = a.ssq_ld, sa.inv_k = a.inv_k, sa.eps = a.eps;
-  sa.rstd_out = a.part + a.part_floats, sa.temporal = g_exp_temporal, sa.rstd_wg = g_rstd_wg;
-  const size_t need8 = (size_t)8 * nt * 9 * 128;
-  if (a.part_floats < need8) return SLICES_UNSUPPORTED;
-  sa.n_groups = nt;
-  if (epi == EPI_STORE) {
-    if (spw != 16) return SLICES_UNSUPPORTED;
-    sa.G = (nt + 31) / 32;
-    RC_(launch_slices_k<1, 9, 8, 16, 16, 1, EPI_STORE>(sa, a.wf, st));
-    launch_finish<EPI_STORE, 1, 9, 8>(a, nt, st);
-  } else if (epi == EPI_QKV) {
-    if (spw != 16 || (nt % 16) != 0 || nt / 16 * 4 > 256) return SLICES_UNSUPPORTED;
-#ifdef DD_TIMING_EXPERIMENTS
-    if (g_seq_quads && !a.wf && nt % 8 == 0 && nt / 8 <= 128) {
-      sa.G = nt / 8;                                     // one tile per wave, 2 * G workgroups
-      RC_(launch_slices_seq_quads<9, 4, 1, EPI_QKV>(sa, a.wf, st));
-      launch_finish<EPI_QKV, 1, 9, 2>(a, nt, st);
-      return DD_OK;
-    }
-#endif
-    sa.G = g_exp_G[0] > 0 ? g_exp_G[0] : nt / 16;
-    DD_REQUIRE((nt + 8 * sa.G - 1) / (8 * sa.G) <= 2, "gemv_slices_seq: %d tiles over %d workgroups per pair", nt, sa.G);
-    if (g_exp_U9 == 8) RC_(launch_slices_seq<9, 8, 2, EPI_QKV>(sa, a.wf, st));
-    else RC_(launch_slices_seq<9, 4, 2, EPI_QKV>(sa, a.wf, st));
-    launch_finish<EPI_QKV, 1, 9, 4>(a, nt, st);
-  } else if (epi == EPI_RESID) {
-    if (spw == 16 && g_exp_G[1] == -2 && (nt + 8 * 32 - 1) / (8 * 32) <= 1) {
-      // (A/B, tuning key 18 = -2) slice PAIRS, one slice resident at a time, one tile per wave on 4 * 32 = 128 workgroups: half the partial sums
-      sa.G = 32;
-      RC_(launch_slices_seq<9, 8, 1, EPI_RESID>(sa, a.wf, st));
-      launch_finish<EPI_RESID, 1, 9, 4>(a, nt, st);
-      return DD_OK;
-    }
-    if (spw == 16) {
-      // two tiles per wave on 8 * 16 = 128 workgroups at N = 4096: alone 14.7 us against 11.2 with one tile per wave on 256, but inside
-      // the step, beside the other branch's kernels, the half-chip grid wins (20.9 vs 21.4 ms per 32-lane step; tuning key 18)
-      sa.G = g_exp_G[1] > 0 ? g_exp_G[1] : (nt + 15) / 16;
-      RC_(launch_slices_k<1, 9, 8, 16, 16, 1, EPI_RESID>(sa, a.wf, st));
-    } else {
-      sa.G = (nt + 7) / 8;
-      if (spw == 43) RC_(launch_slices_k<1, 9, 8, 43, 8, 1, EPI_RESID>(sa, a.wf, st));
-      else RC_(launch_slices_k<1, 9, 8, 56, 8, 1, EPI_RESID>(sa, a.wf, st));
-    }
-    launch_finish<EPI_RESID, 1, 9, 8>(a, nt, st);
-  } else if (spw == 16 && (4 * ((nt + 23) / 24) > 256 || g_exp_G[2] == -2)) {      // (A/B, tuning key 19 = -2: single slices for every gate/up)
-    // more gate/up tiles than three per wave of one round of slice PAIRS (Mistral-7B: 1792 tiles): single slices, tiles walked per wave
-    sa.G = 32;
-    RC_(launch_slices_k<1, 9, 8, 16, 16, 1, EPI_SILU>(sa, a.wf, st));
-    launch_finish<EPI_SILU, 2, 9, 8>(a, a.n_tiles, st);
-  } else {
-    if (spw != 16) return SLICES_UNSUPPORTED;
-#ifdef DD_TIMING_EXPERIMENTS
-    if (g_seq_quads && !a.wf) {
-      sa.G = g_seq_quads == 2 ? 128 : (nt + 15) / 16;    // two tiles per wave
-      if ((nt + 8 * sa.G - 1) / (8 * sa.G) <= 2) {
-        RC_(launch_slices_seq_quads<9, 4, 2, EPI_SILU>(sa, a.wf, st));
-        launch_finish<EPI_SILU, 2, 9, 2>(a, a.n_tiles, st);
-        return DD_OK;
-      }
-    }
-#endif
-    sa.G = g_exp_G[2] > 0 ? g_exp_G[2] : (nt + 23) / 24;
-    DD_REQUIRE(g_exp_G[2] == -3 || (nt + 8 * sa.G - 1) / (8 * sa.G) <= 3, "gemv_slices_seq: %d tiles over %d workgroups per pair", nt, sa.G);
-    // (four weight requests in flight per wave: with eight, three tiles per wave and nine planes the kernel needs 257 registers and
-    // spills 28 bytes per lane to private scratch — that instantiation is gone, build.py refuses kernels with scratch)
-    if (g_exp_G[2] == -3) {
-      // (A/B, tuning key 19 = -3) two tiles per wave on 4 * ceil(nt / 16) workgroups (11008: 344, more than one per CU): 196 instead of 236
-      // VGPRs, so that the rider sweeps' attention (94) fits beside this kernel too
-      sa.G = (nt + 15) / 16;
-      RC_(launch_slices_seq<9, 4, 2, EPI_SILU>(sa, a.wf, st));
-    } else if (g_exp_U9 == 8) {
-      // (tuning key 29 = 8) eight weight requests in flight per wave: possible since the folded sums of two tiles share a register set (round 5)
-      RC_(launch_slices_seq<9, 8, 3, EPI_SILU>(sa, a.wf, st));
-    } else
-    RC_(launch_slices_seq<9, 4, 3, EPI_SILU>(sa, a.wf, st));
-    launch_finish<EPI_SILU, 2, 9, 4>(a, a.n_tiles, st);
-  }
-  return DD_OK;
+
+int ddk_gemv_plan(int epi, int planes, int wq, int wf, int S, int n_tiles, int half_planes, size_t part_floats, char* name, size_t name_cap,
+                  int* grid, int* finish_np) {
+  DD_REQUIRE(name && name_cap && grid && finish_np, "gemv_plan: null output");
+  SlicePlan p;
+  name[0] = 0, *grid = *finish_np = 0;
+  if (!plan_slices(epi, planes, wq, wf, S, n_tiles, half_planes, part_floats, epi != EPI_RESID, p)) return DD_GEMV_NO_SLICES;
+  *grid = p.grid, *finish_np = p.fin_np;
+  char last[sizeof(g_last_kernel)];
+  memcpy(last, g_last_kernel, sizeof(last));                  // (the name goes through NOTE_KERNEL; nothing was launched)
+  const int rc = launch_slice_kernel(p, nullptr, wf, nullptr);
+  snprintf(name, name_cap, "%s", g_last_kernel);
+  memcpy(g_last_kernel, last, sizeof(last));
+  return rc;
 }
 
 int ddk_gemv_groups(int epi, const GemvArgs& a, hipStream_t st) {
@@ -1496,20 +1360,13 @@ int ddk_gemv_groups(int epi, const GemvArgs& a, hipStream_t st) {
   DD_REQUIRE(a.n_groups == 2 || a.n_groups == 4 || a.n_groups == 8 || a.n_groups == 9, "gemv_groups: %d groups (2, 4, 8 or 9)", a.n_groups);
   DD_REQUIRE(!a.half_planes || (((a.n_groups == 8 && a.half_planes == 8) || (a.n_groups == 9 && a.half_planes == 7)) && a.nb <= 4 && !a.wq && a.part && g_gemv_slices),
              "gemv_groups: half planes take an eight- or nine-plane pass of 16-bit weights, K <= 4");
-  if (a.n_groups == 9) {
-    int rs = a.part ? try_slices9(epi, a, st) : SLICES_UNSUPPORTED;
-    DD_REQUIRE(rs != SLICES_UNSUPPORTED, "gemv_groups: no nine-plane kernel for this matrix (K = %d, %d tiles, weight storage %d)", a.S * 32, a.n_tiles, a.wq);
-    if (rs != DD_OK) return rs;
+  SlicePlan p;
+  const bool planned = a.part && plan_slices(epi, a.n_groups, a.wq, a.wf, a.S, a.n_tiles, a.half_planes, a.part_floats, a.ssq_in != nullptr, p);
+  DD_REQUIRE(planned || a.n_groups != 9, "gemv_groups: no nine-plane kernel for this matrix (K = %d, %d tiles, weight storage %d)", a.S * 32, a.n_tiles, a.wq);
+  if (planned) {
+    RC_(launch_slices(epi, a, p, st));
     DD_CHECK_LAUNCH();
     return DD_OK;
-  }
-  if (g_gemv_slices && a.part) {
-    int rs = a.n_groups == 2 ? try_slices<2>(epi, a, st) : (a.n_groups == 4 ? try_slices<4>(epi, a, st) : try_slices<8>(epi, a, st));
-    if (rs != SLICES_UNSUPPORTED) {
-      if (rs != DD_OK) return rs;
-      DD_CHECK_LAUNCH();
-      return DD_OK;
-    }
   }
   DD_REQUIRE(!a.half_planes, "gemv_groups: no eight-plane kernel for this matrix (half planes have no fallback)");
   if (a.n_groups == 8) {

@@ -174,7 +174,11 @@ int ddk_gemv_groups(int epi, const GemvArgs& a, hipStream_t st);   // the same f
 int ddk_tp_finish(const float* gather, int W, size_t slot_floats, int nb, float* x, int N, const float* normw, u32x4_t* xop_next,
                   float* ssq_out, int ssq_ld, int wf, hipStream_t st);      // decode rows: + k_gemv's EPI_RESID epilogue
 int ddk_tp_add_rows(float* x, const float* gather, int W, size_t n, hipStream_t st);   // prefill rows: x += sum of the slots
-void ddk_set_tuning(int key, int value);
+// The slice-resident kernel ddk_gemv_groups would launch for these arguments of GemvArgs (no launch, no HIP call): its name as a kernel
+// trace prints it, its grid, the partial sums per output its finishing kernel adds.  DD_GEMV_NO_SLICES: none (k_gemv_groups runs).
+#define DD_GEMV_NO_SLICES 1
+int ddk_gemv_plan(int epi, int planes, int wq, int wf, int S, int n_tiles, int half_planes, size_t part_floats, char* name, size_t name_cap,
+                  int* grid, int* finish_np);
 void ddk_set_gemv_slices(int on);
 void ddk_set_gemm_big_rows(int rows);  // dd_set_tuning key 16: rows from which the prefill GEMM uses the 128 x 512 LDS-staged block (0: never; same bits)
 void ddk_set_gemm_dma(int form);       // dd_set_tuning key 20: big block of the prefill GEMM — 1 (default): LDS-DMA, 160 or 128 rows chosen per launch; 10 / 8: always that LDS-DMA block; 0: the register-staged 128 x 512 block; same bits

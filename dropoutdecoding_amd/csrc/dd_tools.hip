@@ -73,21 +73,32 @@ extern "C" int dd_lm_time_gemv(dd_lm* h, int which, int nb, int iters, float* me
 }
 
 // Experiment knobs (A/B switches of kernel variants; every setting produces the same bits).  Keys as the tools/ scripts and
-// DESIGN.md quote them: 0 = GEMV weight tiles in flight per wave (4/8/16), 4 = ring (1) or batch (0) request order of the 8-row
-// GEMV, 9 = sequences per member sweep in dd_lm_group_step (1, 2, 4, 8), 10 = workgroups per group of 8 members in the grouped
-// decode attention, 12 = prefill attention on the matrix cores, 17 / 18 / 19 = workgroups per K slice of the 64-row qkv / o_proj /
-// gate-up GEMV (18 < 0: eight-plane o_proj kernel; 19 < 0: single K slices for gate/up), 21 = key tiles per workgroup of the
+// DESIGN.md quote them: 9 = sequences per member sweep in dd_lm_group_step (1, 2, 4, 8), 10 = workgroups per group of 8 members in the grouped
+// decode attention, 12 = prefill attention on the matrix cores, 21 = key tiles per workgroup of the
 // fp16-cache decode attention, 22 = all-tiles form of that attention, 23 = concurrent member sweeps of a
-// classic group step, 24 = four-columns-per-thread finishing kernel of the slice GEMVs (bit mask over the epilogues), 26 = rider form of the
+// classic group step, 26 = rider form of the
 // group step (0: the classic form always), 27 = the riding rows' attention inside the members' launches, 28 = branches of the rider
-// form (1..4), 29 = weight requests in flight per wave of the nine-plane qkv / gate-up kernels (4 or 8), 30 = half planes for K <= 4, 31 = half
+// form (1..4), 30 = half planes for K <= 4, 31 = half
 // planes (classic form) before the rider form for line-ups that are not whole groups of fourteen, 33 = rider rings in stages (masks
 // between the stages on the caller's stream), 34 = the lanes mask sampler in one of its 1,024-thread forms (dd_sampler_block.h, this library only: 1 =
 // round 3's, 616 bytes of private scratch per lane; 2 = the checking form; 3 = round 4's product kernel; 0 = the product's one-wave sampler), 48 = the
 // dynamic-LDS request of those forms (0: the 76 KiB they use, 1: 156 KiB, n: n KiB); the product switches
-// (8, 11, 13-16) are forwarded to dd_set_tuning.  Every call bumps the graph-key epoch: steps captured under other settings are not replayed.
-extern int g_exp_G[4];
-extern int g_attn16_tpw, g_attn16_full, g_finish4, g_attn16_gh_all, g_attn32_lds_pad, g_attn32_nopk, g_attn_comb_pre;
+// (8, 11, 13-16) are forwarded to dd_set_tuning.  Keys 1 (non-temporal loads) and 2 (k-step interleave) of the 8-row GEMV are settled at 1 and
+// accepted as no-ops.  Every call bumps the graph-key epoch: steps captured under other settings are not replayed.
+//
+// Retired keys (refused as unknown; the variants they switched are no longer compiled).  Key: what it switched; what was measured:
+//   0   weight tiles in flight per wave of the 8-row GEMV (4 / 8 / 16): 4 and 16 measured equal or worse than 8 (round 1, DESIGN_HISTORY.md)
+//   4   ring instead of batch request order of the 8-row GEMV: equal or worse, gate/up 10 % slower (round 1, DESIGN_HISTORY.md)
+//   17  workgroups per slice pair of the 64- / 72-row qkv GEMV (< 0: single slices): one round of 4 * G <= 256 workgroups; 32 lanes, the
+//       choices of 17-19 together: 32.6 -> 31.6 ms per group step
+//   18  the same for o_proj (< 0: the eight-plane kernel, 13.5 us alone against 10.4 for two half passes of four planes; -2: slice pairs
+//       at nine planes); nine planes on 128 workgroups: alone 14.7 against 11.2 us on 256, inside the step 20.9 vs 21.4 ms per 32-lane step
+//   19  the same for gate/up (-2: single slices; -3: two tiles per wave at nine planes): 58 per pair 27.25 ms per 32-lane step, single
+//       slices 27.75, 64 per pair 28.6, 86 per pair 29.1
+//   24  k_gemv_finish, the one-column-per-thread finishing kernel, per epilogue (bit mask; round 3): k_gemv_finish4 replaced it, same bits
+//   29  eight instead of four weight requests in flight per wave of the nine-plane qkv / gate-up kernels: 35.8 vs 35.5 ms per step (round 5)
+//   52  the nine-plane fp8 slice kernel without the operand-fragment ring (XPF = 0; round 6): the ring is the product, same bits
+extern int g_attn16_tpw, g_attn16_full, g_attn16_gh_all, g_attn32_lds_pad, g_attn32_nopk, g_attn_comb_pre;
 void dd_engine_set_pairs(int on);
 void dd_engine_set_branches(int n);
 void dd_engine_set_rider(int on);
@@ -100,7 +111,7 @@ void dd_engine_set_fp32_fork(int on);
 void dd_engine_set_mask_branches(int on);
 void dd_engine_set_attn_masked(int mode);
 void dd_engine_set_unmask(int m);
-extern int g_exp_U9, g_exp_temporal, g_rmsnorm16, g_prefill_attn16, g_attn16_ride_pf, g_sampler_lds_pad, g_seq_prog, g_rstd_wg, g_fp8_xpf, g_seq_quads, g_gemv_loop;
+extern int g_exp_temporal, g_rmsnorm16, g_prefill_attn16, g_attn16_ride_pf, g_sampler_lds_pad, g_seq_prog, g_rstd_wg, g_seq_quads, g_gemv_loop;
 void dd_dropout_set_lanes_sampler_scratch(int on);   // dd_dropout.hip compiled with -DDD_KEEP_SCRATCH_SAMPLER (this library only)
 void dd_dropout_set_sampler_dbg(uint32_t* buf);
 uint32_t dd_dropout_sampler_dbg_tag();
@@ -116,20 +127,17 @@ extern "C" unsigned int dd_tools_sampler_dbg_launches(void) { return dd_dropout_
 extern "C" int dd_tools_set_tuning(int key, int value) {
   dd_engine_bump_epoch();
   if (key == 8 || key == 11 || (key >= 13 && key <= 16) || key == 20) return dd_set_tuning(key, value);
-  DD_REQUIRE(key == 0 || key == 1 || key == 2 || key == 4 || key == 9 || key == 10 || key == 12 || (key >= 17 && key <= 19) || (key >= 21 && key <= 24) || (key >= 26 && key <= 31) || key == 33 || key == 34 || key == 36 || key == 37 || key == 38 || key == 39 || key == 40 || key == 41 || key == 42 || key == 43 || key == 45 || key == 46 || key == 47 || key == 48 || key == 49 || key == 50 || key == 52 || key == 53 || key == 54 || key == 55,
+  DD_REQUIRE(key == 1 || key == 2 || key == 9 || key == 10 || key == 12 || (key >= 21 && key <= 23) || (key >= 26 && key <= 28) || key == 30 || key == 31 || key == 33 || key == 34 || key == 36 || key == 37 || key == 38 || key == 39 || key == 40 || key == 41 || key == 42 || key == 43 || key == 45 || key == 46 || key == 47 || key == 48 || key == 49 || key == 50 || key == 53 || key == 54 || key == 55,
              "dd_tools_set_tuning: unknown key %d", key);
   if (key == 9) dd_engine_set_pairs(value);
   else if (key == 10) ddk_set_attn_split(value);
   else if (key == 12) ddk_set_prefill_mfma(value);
-  else if (key >= 17 && key <= 19) g_exp_G[key - 17] = value;
   else if (key == 21) g_attn16_tpw = value;
   else if (key == 22) g_attn16_full = value;
   else if (key == 23) dd_engine_set_branches(value);
-  else if (key == 24) g_finish4 = value;
   else if (key == 26) dd_engine_set_rider(value);
   else if (key == 27) dd_engine_set_ride_beside(value);
   else if (key == 28) dd_engine_set_rider_branches(value);
-  else if (key == 29) g_exp_U9 = value;
   else if (key == 30) dd_engine_set_half_planes(value);
   else if (key == 31) dd_engine_set_half_planes_first(value);
   else if (key == 33) dd_engine_set_rider_staged(value);
@@ -148,11 +156,10 @@ extern "C" int dd_tools_set_tuning(int key, int value) {
   else if (key == 48) g_sampler_lds_pad = value;
   else if (key == 49) g_seq_prog = value;
   else if (key == 50) g_rstd_wg = value;
-  else if (key == 52) g_fp8_xpf = value;
   else if (key == 53) g_seq_quads = value;
   else if (key == 54) g_gemv_loop = value;
   else if (key == 55) g_attn_comb_pre = value;
-  else ddk_set_tuning(key, value);      // 0, 4; 1 and 2 are settled (accepted, ignored)
+  // (1 and 2 are settled: accepted, ignored)
   return DD_OK;
 }
 
@@ -160,6 +167,10 @@ extern "C" int dd_tools_set_tuning(int key, int value) {
 // prints it (template arguments included): bench.py matches its roofline kernel against rocprofv3 output by this string.
 const char* ddk_last_gemv_kernel();
 extern "C" const char* dd_tools_last_gemv_kernel(void) { return ddk_last_gemv_kernel(); }
+extern "C" int dd_tools_gemv_plan(int epi, int planes, int wq, int wf, int S, int n_tiles, int half_planes, size_t part_floats, char* name_out,
+                                  size_t name_cap, int* grid_out, int* finish_np_out) {
+  return ddk_gemv_plan(epi, planes, wq, wf, S, n_tiles, half_planes, part_floats, name_out, name_cap, grid_out, finish_np_out);
+}
 
 // Calibration: plain streaming READ bandwidth of this device over a large buffer (grid-stride 16-byte loads, 8 per
 // thread in flight), timed with HIP events.  bench.py reports it next to the 8 TB/s spec peak so the roofline

@@ -16,7 +16,7 @@ int dd_lm_time_sweep(dd_lm* h, int nb, int iters, float* mean_ms_out, void* stre
 
 /* Time one decode GEMV kind in isolation (HIP events on `stream`), cycling over the layers' weights so every
  * launch streams bytes that are not cache-resident. which: 0 qkv, 1 o_proj, 2 gate/up, 3 down_proj; nb = rows (1..8, or
- * 16 / 32 / 64 = the two- / four- / eight-plane kernels of the lanes path: k_gemv_slices + k_gemv_finish, or k_gemv_groups).
+ * 16 / 32 / 64 / 72 = the two- / four- / eight- / nine-plane kernels of the lanes path: k_gemv_slices + k_gemv_finish4, or k_gemv_groups).
  * which + 8: the slice-resident path's STREAMING kernel alone (without its finishing kernel) — the kernel
  * whose duration rocprofv3's kernel trace reports under the name dd_tools_last_gemv_kernel() returns afterwards.
  * bytes_per_launch_out = algorithmic (weight) bytes of one launch. */
@@ -27,20 +27,29 @@ int dd_lm_time_gemv(dd_lm* h, int which, int nb, int iters, float* mean_ms_out, 
  * thread's last GEMV launch used. */
 const char* dd_tools_last_gemv_kernel(void);
 
+/* Which slice-resident kernel a 16- / 32- / 64- / 72-row decode GEMV (planes = 2, 4, 8, 9) would run, decided on the host without a
+ * launch (no GPU needed).  epi: 0 logits (lm_head), 1 residual (o_proj, down_proj), 2 SiLU (gate/up), 3 qkv; wq: 0 16-bit, 1 fp8,
+ * 2 MXFP4 tiles; wf: 1 = fp16 instead of bf16; S = K / 32; n_tiles = 16-row tiles of the matrix (epi 2: gate/up PAIRS); half_planes
+ * as in the engine (0, or 8 / 7 at eight / nine planes); part_floats = floats of the partial-sum buffer.  Every epilogue but the
+ * residual one is taken to carry the folded RMSNorm, as in the engine.  Returns 0 and fills name_out (the streaming kernel as a kernel
+ * trace and dd_tools_last_gemv_kernel() name it, under the current switch settings), grid_out (its workgroups) and finish_np_out
+ * (partial sums per output that k_gemv_finish4 adds); or 1 = no slice kernel for this shape: k_gemv_groups runs (nine planes: an error). */
+int dd_tools_gemv_plan(int epi, int planes, int wq, int wf, int S, int n_tiles, int half_planes, size_t part_floats, char* name_out,
+                       size_t name_cap, int* grid_out, int* finish_np_out);
+
 /* Streaming READ bandwidth (GB/s) this device delivers over buf_dev[bytes] (bytes >= 1 MiB; use a buffer much larger than
  * the 256 MiB Infinity Cache), HIP events on `stream`. */
 int dd_hbm_read_bench(const void* buf_dev, size_t bytes, int iters, int n_blocks, float* gbs_out, void* stream);
 
 /* A/B switches of kernel variants (every setting produces the same bits); keys as tools/ and DESIGN.md quote them:
- * 0 GEMV weight tiles in flight per wave, 4 ring / batch request order of the 8-row GEMV, 9 sequences per member sweep of
+ * 9 sequences per member sweep of
  * dd_lm_group_step (1, 2, 4, 8), 10 workgroups per group of 8 members in the grouped decode attention, 12 prefill attention
- * on the matrix cores, 17 / 18 / 19 workgroups per K slice of the 64-row qkv / o_proj / gate-up GEMV, 21 key tiles per
+ * on the matrix cores, 21 key tiles per
  * workgroup of the fp16-cache decode attention, 22 all-tiles form of that attention, 23 member sweeps of a group step that
- * run concurrently (1..4), 24 four-columns-per-thread finishing kernel of the slice GEMVs (bit mask over the epilogues
- * EPI_STORE / RESID / SILU / QKV, default 15; 0: the one-column kernel it replaced), 26 rider form of the group step (default 1;
+ * run concurrently (1..4), 26 rider form of the group step (default 1;
  * 0: always the classic form: one fused un-masked sweep + the member sweeps), 27 the riding rows' attention inside the members'
- * launches (default 1), 28 branches of the rider form (1..4, default 4), 29 weight requests in flight per wave of the nine-plane
- * qkv / gate-up kernels (4 or 8, default 4), 30 half planes for K <= 4 (two sequences per operand plane, default 1), 31 half planes
+ * launches (default 1), 28 branches of the rider form (1..4, default 4),
+ * 30 half planes for K <= 4 (two sequences per operand plane, default 1), 31 half planes
  * before the rider form where both apply and the line-up is not whole groups of fourteen (default 1), 33 the rider form's rings in stages with
  * the masks of the groups whose rows rode sampled between the stages on the caller's stream (default 1; 0: on the branches), 34 the lanes
  * mask sampler in one of the 1,024-thread forms this library keeps (csrc/dd_sampler_block.h; default 0 = the product's one-wave kernel; 1 = round 3's
@@ -59,11 +68,11 @@ int dd_hbm_read_bench(const void* buf_dev, size_t bytes, int iters, int n_blocks
  * (so that it cannot share a CU with a slice GEMV), 40 the branches' streams on disjoint CU masks, 41 CU-mask only the attention launches,
  * 42 bit mask of kernel families launched on the UNMASKED stream while 40 is on (1 embed, 2 GEMVs, 4 attention, 8 finishing kernels),
  * 43 the fp32-cache tile pass with scalar instead of packed FP32 multiply-adds in its P.V step (tools library only: the product library has
- * no packed FP32 at all), 52 (round 6) the nine-plane fp8 slice kernel's operand fragments through a ring read five ahead of their MFMAs
- * (default 1; 0: where the compiler requests them; same bits), 53 (round 6, TIMING ONLY: sums in an order no other width produces) four K slices
+ * no packed FP32 at all), 53 (round 6, TIMING ONLY: sums in an order no other width produces) four K slices
  * per workgroup in the nine-plane qkv / gate-up kernels (1: 96 / 86 workgroups per quad, 2: gate/up on 128), 54 (round 6) the 8-row GEMV that keeps
  * the rows' operand in registers and walks several tile groups per workgroup (k_gemv_loop: default 1 = where the tile count is a multiple of 256;
- * 0: never; n > 1: n workgroups for every K = 4096 matrix; same bits).  Keys of
+ * 0: never; n > 1: n workgroups for every K = 4096 matrix; same bits).  Keys 0, 4, 17-19, 24, 29 and 52 switched
+ * GEMV variants whose experiments are settled: they are refused like any unknown key (csrc/dd_tools.hip lists what each measured).  Keys of
  * dd_set_tuning are forwarded.  Every call starts a new epoch of the step-graph
  * keys: a step captured under other settings is never replayed. */
 int dd_tools_set_tuning(int key, int value);

@@ -157,3 +157,38 @@ def test_progressive_stage_in_leaves_the_same_bits(E, n_lanes):
             np.testing.assert_array_equal(x, y)
     for e in reversed(engines):
         e.close()
+
+
+def test_gemv_plan_names_the_kernel_that_runs(E):
+    """dd_tools_gemv_plan (the host-side decision of csrc/dd_gemv.hip plan_slices, tabulated without a GPU in tests/test_host_logic.py)
+    against what ddk_gemv_groups launches: every layer matrix of the two 7B widths in bf16, fp8 and MXFP4 at 16 / 32 / 64 / 72 rows
+    (72: where the format has nine-plane kernels).  Where the plan names a slice kernel that kernel runs; where it says none, the
+    wave-split k_gemv_groups does.  The retired experiment keys are refused, not ignored."""
+    import ctypes
+    from dropoutdecoding_amd import _lib
+    T = _lib.load_tools()
+    d, V = 4096, 2048
+    emb = (torch.randn(30, d, generator=torch.Generator().manual_seed(4)) * 0.5).cuda()
+    for fmt, wq, dff, Hkv in (("bf16", 0, 11008, 32), ("fp8", 1, 14336, 8), ("mxfp4", 2, 11008, 32)):
+        e = E.DropoutEngine(E.LMConfig(V, d, dff, 2, 32, Hkv, 128, 1e-5, 10000.0), family="llava-1.5", max_seq=96, max_visual=24, seed=1,
+                            weight_format=fmt, kv_format="fp16", lib=T)
+        e.load_synthetic(seed=3, std=0.02)
+        e.prefill(emb, 2, 24)
+        qkv_tiles = (32 + 2 * Hkv) * 128 // 16
+        part_floats = 8 * max(qkv_tiles, d // 16, 2 * dff // 16, V // 16) * 9 * 128          # the engine's partial-sum buffer
+        # (epilogue, S = K / 32, n_tiles) of dd_lm_time_gemv's matrices 0..3: qkv, o_proj, gate/up (pairs), down_proj
+        mats = [(3, d // 32, qkv_tiles), (1, d // 32, d // 16), (2, d // 32, dff // 16), (1, dff // 32, d // 16)]
+        for which, (epi, S, nt) in enumerate(mats):
+            for rows in (16, 32, 64) + ((72,) if fmt != "mxfp4" else ()):
+                name, grid, np_ = ctypes.create_string_buffer(96), ctypes.c_int(), ctypes.c_int()
+                rc = T.dd_tools_gemv_plan(epi, rows // 8, wq, 0, S, nt, 0, part_floats, name, len(name), ctypes.byref(grid), ctypes.byref(np_))
+                assert rc in (0, 1), (fmt, which, rows, rc)
+                e.time_gemv(which, rows, 1)
+                ran = e.last_gemv_kernel()
+                if rc == 0:
+                    assert ran == name.value.decode(), (fmt, which, rows)
+                else:
+                    assert ran.startswith("k_gemv_groups<"), (fmt, which, rows, ran)
+        e.close()
+    assert T.dd_tools_set_tuning(17, 1) != 0 and T.dd_tools_set_tuning(24, 0) != 0
+    assert T.dd_tools_set_tuning(1, 1) == 0                  # (settled earlier, still accepted and ignored)

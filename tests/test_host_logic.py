@@ -1,5 +1,6 @@
 """Host-side logic of the drop-in wrappers on CPU (no GPU, no library calls): image-span bookkeeping for both
-processor layouts, error behaviour, return layouts, EOS handling, seed bookkeeping, fp8 quantiser round trip."""
+processor layouts, error behaviour, return layouts, EOS handling, seed bookkeeping, fp8 quantiser round trip; and the table of which slice
+kernel a wide decode GEMV runs (the one test here that loads the built library: host calls only)."""
 import os
 
 import numpy as np
@@ -238,3 +239,104 @@ def test_tensor_parallel_shards_reassemble_the_layer():
     assert torch.allclose(part, full, rtol=1e-4, atol=1e-3) and torch.allclose(o_part, o_full, rtol=1e-4, atol=1e-3)
     with pytest.raises(ValueError):
         lm.tp_local_config(cfg, 4)                        # 2 kv heads do not split over 4 ranks
+
+
+# ---- which slice kernel a 16- / 32- / 64- / 72-row decode GEMV runs (csrc/dd_gemv.hip plan_slices through dd_tools_gemv_plan) ----
+# The 7B families' matrices as GemvArgs describes them: (epilogue, S = K / 32, n_tiles; EPI_SILU counts gate/up pairs).
+_STORE, _RESID, _SILU, _QKV = 0, 1, 2, 3
+_LLAVA = {"qkv": (_QKV, 128, 768), "o": (_RESID, 128, 256), "gate_up": (_SILU, 128, 688), "down": (_RESID, 344, 256)}     # d_ff 11008, 32 / 32 heads
+_MISTRAL = {"qkv": (_QKV, 128, 384), "o": (_RESID, 128, 256), "gate_up": (_SILU, 128, 896), "down": (_RESID, 448, 256)}   # d_ff 14336, 32 / 8 heads
+_LM_HEAD = (_STORE, 128, 2000)
+_PART = 8 * 2000 * 9 * 128           # room for every case below
+_KS, _SEQ = "k_gemv_slices<{}, {w}, {}, {}>", "k_gemv_slices_seq<{}, {w}, {}, 2>"
+# {(model, matrix, planes): (kernel name with the weight-format argument left open, grid, partial sums per output) or None = no slice
+# kernel}.  Names as the parent of the commit that introduced the plan printed them on an MI355X (dd_lm_time_gemv +
+# dd_tools_last_gemv_kernel; lm_head from reading its ladders), grids from those ladders by hand: streaming workgroups + one for the rows'
+# rstd where the operand carries the folded RMSNorm (every epilogue but the residual one).
+_PLAN_16BIT = {
+    ("llava", "qkv", 2): (_KS.format("2, 2, 8, 16, 16, 1", "3", "1", w="{w}"), 8 * 24 + 1, 8),        # 384 tile pairs, two per wave
+    ("mistral", "qkv", 2): (_KS.format("2, 2, 8, 16, 16, 1", "3", "1", w="{w}"), 8 * 24 + 1, 8),      # 192 tile pairs, one per wave
+    ("llava", "qkv", 4): (_KS.format("2, 4, 8, 16, 16, 1", "3", "1", w="{w}"), 193, 8),
+    ("mistral", "qkv", 4): (_KS.format("2, 4, 8, 16, 16, 1", "3", "1", w="{w}"), 193, 8),
+    ("llava", "qkv", 8): (_SEQ.format("8, 8, 16, 2", "3", w="{w}"), 4 * 48 + 1, 4),
+    ("mistral", "qkv", 8): (_SEQ.format("8, 8, 16, 2", "3", w="{w}"), 4 * 24 + 1, 4),
+    ("llava", "qkv", 9): (_SEQ.format("9, 4, 16, 2", "3", w="{w}"), 4 * 48 + 1, 4),
+    ("mistral", "qkv", 9): (_SEQ.format("9, 4, 16, 2", "3", w="{w}"), 4 * 24 + 1, 4),
+    ("llava", "o", 2): None, ("mistral", "o", 2): None, ("llava", "o", 4): None, ("mistral", "o", 4): None,
+    ("llava", "o", 8): (_KS.format("1, 4, 8, 16, 16, 1", "1", "1", w="{w}"), 2 * 8 * 16, 8),           # two half passes of four planes
+    ("mistral", "o", 8): (_KS.format("1, 4, 8, 16, 16, 1", "1", "1", w="{w}"), 2 * 8 * 16, 8),
+    ("llava", "o", 9): (_KS.format("1, 9, 8, 16, 16, 1", "1", "0", w="{w}"), 8 * 16, 8),
+    ("mistral", "o", 9): (_KS.format("1, 9, 8, 16, 16, 1", "1", "0", w="{w}"), 8 * 16, 8),
+    ("llava", "gate_up", 2): (_KS.format("1, 2, 8, 16, 16, 2", "2", "1", w="{w}"), 4 * 64 + 1, 4),
+    ("mistral", "gate_up", 2): (_KS.format("1, 2, 8, 16, 16, 2", "2", "1", w="{w}"), 4 * 64 + 1, 4),
+    ("llava", "gate_up", 4): (_KS.format("1, 4, 8, 16, 16, 2", "2", "1", w="{w}"), 257, 4),
+    ("mistral", "gate_up", 4): (_KS.format("1, 4, 8, 16, 16, 2", "2", "1", w="{w}"), 257, 4),
+    ("llava", "gate_up", 8): (_SEQ.format("8, 8, 16, 3", "2", w="{w}"), 4 * 58 + 1, 4),                # 1376 tiles, three per wave
+    ("mistral", "gate_up", 8): (_KS.format("1, 8, 8, 16, 16, 1", "2", "0", w="{w}"), 8 * 42 + 1, 8),   # 1792 tiles: single slices
+    ("llava", "gate_up", 9): (_SEQ.format("9, 4, 16, 3", "2", w="{w}"), 4 * 58 + 1, 4),
+    ("mistral", "gate_up", 9): (_KS.format("1, 9, 8, 16, 16, 1", "2", "0", w="{w}"), 8 * 32 + 1, 8),
+    ("llava", "down", 2): (_KS.format("1, 2, 8, 43, 16, 1", "1", "0", w="{w}"), 256, 8),
+    ("llava", "down", 4): (_KS.format("1, 4, 8, 43, 16, 1", "1", "0", w="{w}"), 256, 8),
+    ("llava", "down", 8): (_KS.format("1, 8, 8, 43, 8, 1", "1", "0", w="{w}"), 256, 8),
+    ("llava", "down", 9): (_KS.format("1, 9, 8, 43, 8, 1", "1", "0", w="{w}"), 256, 8),
+    ("mistral", "down", 2): (_KS.format("1, 2, 8, 56, 16, 1", "1", "0", w="{w}"), 256, 8),
+    ("mistral", "down", 4): (_KS.format("1, 4, 8, 56, 16, 1", "1", "0", w="{w}"), 256, 8),
+    ("mistral", "down", 8): (_KS.format("1, 8, 8, 56, 8, 1", "1", "0", w="{w}"), 256, 8),
+    ("mistral", "down", 9): (_KS.format("1, 9, 8, 56, 8, 1", "1", "0", w="{w}"), 256, 8),
+    ("any", "lm_head", 2): None,
+    ("any", "lm_head", 4): (_KS.format("1, 4, 8, 16, 16, 2", "0", "1", w="{w}"), 4 * 64 + 1, 4),
+    ("any", "lm_head", 8): (_KS.format("1, 8, 8, 16, 16, 1", "0", "0", w="{w}"), 8 * 63 + 1, 8),
+    ("any", "lm_head", 9): (_KS.format("1, 9, 8, 16, 16, 1", "0", "0", w="{w}"), 8 * 63 + 1, 8),
+}
+_PLAN_FP8 = {       # Mistral-7B, fp8 tiles: whole slices of 8 (K = 4096) or 28 (K = 14336) 64-k steps; at most one workgroup per CU
+    ("qkv", 2): ("k_gemv_slices_fp8<2, 8, 2, 8, 0, 0>", 4 * 48 + 1, 4), ("o", 2): ("k_gemv_slices_fp8<2, 8, 2, 8, 0, 0>", 4 * 32, 4),
+    ("gate_up", 2): ("k_gemv_slices_fp8<2, 8, 2, 8, 0, 0>", 4 * 64 + 1, 4), ("down", 2): ("k_gemv_slices_fp8<2, 28, 1, 7, 0, 0>", 8 * 32, 8),
+    ("qkv", 4): ("k_gemv_slices_fp8<4, 8, 2, 8, 0, 0>", 4 * 48 + 1, 4), ("o", 4): ("k_gemv_slices_fp8<4, 8, 2, 8, 0, 0>", 4 * 32, 4),
+    ("gate_up", 4): ("k_gemv_slices_fp8<4, 8, 2, 8, 0, 0>", 4 * 64 + 1, 4), ("down", 4): ("k_gemv_slices_fp8c<4, 28, 7, 7, 0>", 8 * 32, 8),
+    ("qkv", 8): ("k_gemv_slices_fp8<8, 8, 1, 8, 0, 0>", 8 * 32 + 1, 8), ("o", 8): ("k_gemv_slices_fp8<8, 8, 1, 8, 0, 0>", 8 * 32, 8),
+    ("gate_up", 8): ("k_gemv_slices_fp8<8, 8, 1, 8, 0, 0>", 8 * 32 + 1, 8), ("down", 8): ("k_gemv_slices_fp8c<8, 28, 4, 4, 0>", 8 * 32, 8),
+    ("qkv", 9): ("k_gemv_slices_fp8<9, 8, 1, 8, 0, 6>", 8 * 32 + 1, 8), ("o", 9): ("k_gemv_slices_fp8<9, 8, 1, 8, 0, 6>", 8 * 32, 8),
+    ("gate_up", 9): ("k_gemv_slices_fp8<9, 8, 1, 8, 0, 6>", 8 * 32 + 1, 8), ("down", 9): ("k_gemv_slices_fp8c<9, 28, 4, 4, 0>", 8 * 32, 8),
+}
+
+
+def _gemv_plan(lib, epi, planes, wq, wf, S, n_tiles, half_planes=0, part_floats=_PART):
+    import ctypes
+    name, grid, np_ = ctypes.create_string_buffer(96), ctypes.c_int(-1), ctypes.c_int(-1)
+    rc = lib.dd_tools_gemv_plan(epi, planes, wq, wf, S, n_tiles, half_planes, part_floats, name, len(name), ctypes.byref(grid), ctypes.byref(np_))
+    assert rc in (0, 1), (rc, lib.dd_last_error())
+    return (name.value.decode(), grid.value, np_.value) if rc == 0 else None
+
+
+def test_gemv_plan_names_grid_and_finish_for_the_7b_families():
+    from dropoutdecoding_amd import _lib, build
+    build.build()
+    lib = _lib.load_tools()                                   # plain dlopen + host calls: the plan makes no HIP call
+    shapes = {"llava": _LLAVA, "mistral": _MISTRAL, "any": {"lm_head": _LM_HEAD}}
+    for wf in (0, 1):
+        for (model, matrix, planes), want in _PLAN_16BIT.items():
+            got = _gemv_plan(lib, *((shapes[model][matrix][0], planes, 0, wf) + shapes[model][matrix][1:]))
+            assert got == (want and (want[0].format(w=wf),) + want[1:]), (model, matrix, planes, wf)
+        # half planes (K <= 4: two sequences per operand plane) ride the same eight- / nine-plane kernels
+        for planes, hp in ((8, 8), (9, 7)):
+            for model in ("llava", "mistral"):
+                for matrix, (epi, S, nt) in shapes[model].items():
+                    want = _PLAN_16BIT[(model, matrix, planes)]
+                    assert _gemv_plan(lib, epi, planes, 0, wf, S, nt, half_planes=hp) == (want[0].format(w=wf),) + want[1:], (model, matrix, planes, hp)
+    for (matrix, planes), want in _PLAN_FP8.items():
+        assert _gemv_plan(lib, _MISTRAL[matrix][0], planes, 1, 0, *_MISTRAL[matrix][1:]) == want, (matrix, planes)
+    for planes in (2, 4, 8, 9):
+        assert _gemv_plan(lib, _RESID, planes, 1, 0, 344, 256) is None                   # fp8, K = 11008: not whole 64-k steps per wave
+        for model in (_LLAVA, _MISTRAL):
+            for epi, S, nt in list(model.values()) + [_LM_HEAD]:
+                assert _gemv_plan(lib, epi, planes, 2, 0, S, nt) is None                 # MXFP4: no slice kernels
+        assert _gemv_plan(lib, _QKV, planes, 0, 0, 128, 63) is None                      # fewer than 64 tiles
+        assert _gemv_plan(lib, _SILU, planes, 0, 0, 128, 31) is None                     # (62 gate/up tiles)
+        assert _gemv_plan(lib, _QKV, planes, 1, 0, 128, 63) is None
+    # the partial-sum buffer: eight slabs of tiles x planes x 128 floats (slice pairs up to four planes: four), not one float less
+    for epi, planes, S, nt, need in ((_QKV, 9, 128, 768, 8 * 768 * 9 * 128), (_QKV, 8, 128, 768, 8 * 768 * 8 * 128), (_SILU, 4, 128, 688, 4 * 1376 * 4 * 128),
+                                     (_QKV, 2, 128, 768, 8 * 768 * 2 * 128), (_RESID, 4, 344, 256, 8 * 256 * 4 * 128)):
+        assert _gemv_plan(lib, epi, planes, 0, 0, S, nt, part_floats=need) is not None, (epi, planes)
+        assert _gemv_plan(lib, epi, planes, 0, 0, S, nt, part_floats=need - 1) is None, (epi, planes)
+    assert _gemv_plan(lib, _QKV, 9, 1, 0, 128, 384, part_floats=8 * 384 * 9 * 128 - 1) is None
+    assert _gemv_plan(lib, _SILU, 2, 1, 0, 128, 896, part_floats=4 * 1792 * 2 * 128 - 1) is None
